@@ -8,8 +8,13 @@ HVM4 samples (searched root positions) written per second, whole job.  N>1: ever
 64 games (games are the independent unit; the only exchange is the gather of finished records to
 rank 0, inside the timed region) -> weak scaling.
 
-`--workload planes` keeps the round-1 first bench (configs[1], batched plane-encode of 65 536
-positions); its numbers are also reported under "extra" of the default run, with joint perft.
+A plain run sets up, warms up, times `--steps` steps and prints the line (headline, roofline objects and leg times of
+the timed steps themselves).  `--full` adds everything that takes runs of its own: the CPU port baselines, the same
+engine with 256 games in flight, the plane encoder (configs[1]) and joint perft, under "cpu_baseline" and "extra".
+`--workload planes` times the round-1 first bench (configs[1], batched plane-encode of 65 536 positions) alone.
+
+`--dump-outputs DIR` writes what the last timed step handed to its caller as DIR/<name>.npy (float32 / float64, at
+most 64 MB; larger arrays as a seeded row sample).  Seeds are fixed, so two builds can be compared output for output.
 
 `--gpus N` without a torchrun environment (WORLD_SIZE unset): this process is only a launcher.  Before any
 GPU / HIP call it starts N children of itself, one rank per GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set,
@@ -105,6 +110,52 @@ def cpu_selfplay_baseline(model, nodes, seconds=20.0):
                        f"({torch.get_num_threads()} intra-op threads); {nodes_done / dt:.0f} nodes/s")
 
 
+DUMP_BYTES = {"planes": 40e6, "policy": 16e6, "samples": 4e6}        # --dump-outputs: 60 MB of array data, under the 64 MB limit
+
+
+def _sample_rows(n, row_bytes, max_bytes):
+    """indices of all n rows, or — when they would not fit in max_bytes — of a fixed (seeded, ascending) sample of them"""
+    keep = int(max_bytes // row_bytes)
+    if n <= keep:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+
+
+def selfplay_outputs(rec, cnt):
+    """--dump-outputs of a self-play step: the HVM4 records the step returned (rank 0, after the gather), decoded by the package's
+    own reader.  samples[i] = game_id, nodes, macro_ply, moves_left, team, time_adv, outcome, wdl, root_q of record i (record order);
+    policy = one row (record, board, policy index, probability) per stored policy entry; planes = the u8 input planes of the records
+    listed in planes_rows."""
+    import tempfile
+    import hivemind_amd as hm
+    with tempfile.TemporaryDirectory() as d:
+        hm.write_chunk(os.path.join(d, "step.hvm"), rec, cnt)
+        smp = hm.read_hvm4(os.path.join(d, "step.hvm"))
+    keys = ("game_id", "nodes", "macro_ply", "moves_left", "team", "time_adv", "outcome", "wdl", "root_q")
+    samples = np.array([[s[k] for k in keys] for s in smp], dtype=np.float64).reshape(len(smp), len(keys))
+    policy = np.concatenate([np.zeros((0, 4))] + [np.stack([np.full(len(e), i), np.full(len(e), b), e["index"], e["prob"]], 1)
+                                                  for i, s in enumerate(smp) for b, e in enumerate((s["policy_a"], s["policy_b"]))])
+    rows = _sample_rows(len(smp), 4736 * 4, DUMP_BYTES["planes"])
+    planes = np.array([smp[i]["planes"].reshape(-1) for i in rows], dtype=np.float32).reshape(len(rows), 4736)
+    return {"samples": samples[_sample_rows(len(samples), len(keys) * 8, DUMP_BYTES["samples"])],
+            "policy": policy[_sample_rows(len(policy), 16, DUMP_BYTES["policy"])].astype(np.float32),
+            "planes": planes, "planes_rows": rows.astype(np.float64)}
+
+
+def planes_outputs(out):
+    """--dump-outputs of a plane-encode step: the fp16 planes of a fixed sample of the batch's positions"""
+    rows = _sample_rows(len(out), 4736 * 4, DUMP_BYTES["planes"])
+    planes = out.reshape(len(out), -1)[torch.from_numpy(rows).to(out.device)].float().cpu().numpy()
+    return {"planes": planes, "planes_rows": rows.astype(np.float64)}
+
+
+def dump_outputs(directory, arrays):
+    assert sum(a.nbytes for a in arrays.values()) <= 62e6 and all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def _pmc_traffic(path):
     """bytes per launch by kernel = WRITE_SIZE + corrected FETCH_SIZE of a committed rocprofv3 PMC summary
     (tools/pmc_summary.py; per kernel and counter the grid size with the most launches).  Refused — empty result —
@@ -198,7 +249,7 @@ def bench_stub(steps, warmup, rank, world, dist):
     dt = allred(time.perf_counter() - t0, dist.ReduceOp.MAX if dist else None)
     units = allred(units, dist.ReduceOp.SUM if dist else None)
     return dict(metric="stub units/sec (launcher rehearsal, no GPU)", value=units / dt, unit="units/s", steps=steps, warmup=warmup,
-                ms_per_step=dt / steps * 1e3, dtype="none", config={"workload": "stub"}, roofline=None)
+                ms_per_step=dt / steps * 1e3, dtype="none", config={"workload": "stub"}, roofline=None), units
 
 
 def main():
@@ -211,9 +262,12 @@ def main():
     ap.add_argument("--nodes", type=int, default=400)
     ap.add_argument("--model", default="small", choices=["small", "full"])
     ap.add_argument("--perft-depth", type=int, default=5, help="extra: joint perft depth (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: CPU baselines and the extra workloads")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave the extra workloads out")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step to DIR/<name>.npy")
     args = ap.parse_args()
+    cpu_baselines, extras = args.full and not args.no_cpu_baseline, args.full and not args.no_extra
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -239,8 +293,10 @@ def main():
         else:
             dist.init_process_group(backend)
     if args.workload == "stub":
-        line = bench_stub(args.steps, args.warmup, rank, world, dist)
+        line, units = bench_stub(args.steps, args.warmup, rank, world, dist)
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {"units": np.array([units], dtype=np.float64)})
             line.update({"n_gpus": world, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic",
                          "cpu_baseline": None, "extra": {}})
             print(json.dumps(line), flush=True)
@@ -274,11 +330,13 @@ def main():
 
     extra, cpu, line = {}, None, None
     if args.workload == "planes":
-        steps, warmup = max(args.steps, 50), max(args.warmup, 5)
+        steps, warmup = args.steps, args.warmup
         barrier()
         pl, boards, out, dt = bench_planes(hm, dev, steps, warmup, rank)
         dt = max_over_ranks(dt)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, planes_outputs(out))
+        if rank == 0 and world == 1 and cpu_baselines:
             cpu = cpu_planes_baseline(boards, out)
         line = dict(metric="plane-encode positions/sec (BASELINE configs[1])", value=world * N_POSITIONS * steps / dt, unit="positions/s",
                     steps=steps, warmup=warmup, ms_per_step=dt / steps * 1e3, dtype="u64",
@@ -424,7 +482,9 @@ def main():
                              "transposition_table": {"lookups_that_hit": tot["tt_hits"], "inserts": tot["tt_inserts"],
                                                      "hit_rate": tot["tt_hits"] / max(tot["tt_hits"] + tot["tt_inserts"], 1)},
                              "wall_split_s": {"run": tot["seconds"], "search": tot["search_s"], "prologue": tot["prologue_s"], "raw_policy": tot["raw_s"]}}
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, selfplay_outputs(rec, cnt))
+        if rank == 0 and world == 1 and cpu_baselines:
             cpu = cpu_selfplay_baseline(model, args.nodes)
         line = dict(metric=f"self-play positions/sec @ nodes={args.nodes}", value=samples / dt, unit="positions/s", steps=args.steps,
                     warmup=args.warmup, ms_per_step=dt / args.steps * 1e3, dtype="fp16 net / u64 board / f32 tree",
@@ -432,7 +492,7 @@ def main():
                                         f"(torch.manual_seed(0)), B=8 single-thread reference schedule per game",
                             "games_per_gpu": args.games, "nodes": args.nodes, "sharding": f"games x{world}, record gather only"},
                     roofline=roof)
-        if not args.no_extra and world == 1:
+        if extras and world == 1:
             # the same engine with more games in flight (the 64-game configuration is latency-bound)
             cfg = hm.default_selfplay_config(games=256, nodes=args.nodes, seed=77, concurrent_games=256)
             sp = hm.SelfPlay(cfg, net, device=dev)
@@ -455,9 +515,9 @@ def main():
             extra["rooflines"].append({"bound": "hbm", "achieved": pl["achieved_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                        "frac": pl["hbm_frac"], "traffic": enc, "kernel": "encode_planes_kernel<f16>",
                                        "kernel_ms": pl["kernel_ms"], "algorithmic_bytes_per_launch": pl["algorithmic_bytes_per_launch"]})
-            if rank == 0 and not args.no_cpu_baseline:
+            if rank == 0 and cpu_baselines:
                 extra["plane_encode_64k"]["cpu_baseline"] = cpu_planes_baseline(boards, out, 5.0)
-        if not args.no_extra and args.perft_depth > 0:
+        if extras and args.perft_depth > 0:
             n, secs = hm.perft(args.perft_depth, shard=rank, nshards=world)
             n, secs = int(sum_over_ranks(n)), max_over_ranks(secs)
             extra["perft"] = {"depth": args.perft_depth, "nodes": n, "seconds": secs, "nodes_per_s": n / secs if secs > 0 else None}

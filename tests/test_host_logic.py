@@ -157,6 +157,27 @@ def test_bench_gpus_flag_launches_that_many_ranks():
     assert one["n_gpus"] == 1
 
 
+def test_bench_dump_outputs_writes_float_arrays(tmp_path):
+    """`--dump-outputs DIR` through the launcher-free stub run, and the decoding of a self-play step's records into the dumped arrays."""
+    r = _bench(["--workload", "stub", "--steps", "3", "--warmup", "0", "--dump-outputs", str(tmp_path / "o")])
+    assert r.returncode == 0, r.stderr
+    assert np.load(tmp_path / "o" / "units.npy").tolist() == [30.0]
+    sys.path.insert(0, ROOT)
+    import bench
+    recs = _sample_bytes(7, 411, 12, 1, 255, [(0, 0.5), (100, 0.5)], [(0, 1.0)]) + _sample_bytes(8, 399, 13, 0, 3, [(5, 1.0)], [])
+    out = bench.selfplay_outputs(np.frombuffer(recs, np.uint8), 2)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert out["samples"].tolist() == [[7, 411, 12, 3, 1, 0, 1, 2, 0.25], [8, 399, 13, 3, 0, 0, 1, 2, 0.25]]
+    assert out["policy"].tolist() == [[0, 0, 0, 0.5], [0, 0, 100, 0.5], [0, 1, 0, 1.0], [1, 0, 5, 1.0]]
+    assert out["planes"].shape == (2, 4736) and out["planes_rows"].tolist() == [0, 1]
+    assert np.all(out["planes"][0] == 255) and np.all(out["planes"][1] == 3)
+    # an output over its byte budget is dumped as the same ascending row sample every time
+    rows = bench._sample_rows(1000, 4, 400)
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0) and np.array_equal(rows, bench._sample_rows(1000, 4, 400))
+    bench.dump_outputs(str(tmp_path / "d"), out)
+    assert sorted(os.listdir(tmp_path / "d")) == ["planes.npy", "planes_rows.npy", "policy.npy", "samples.npy"]
+
+
 def test_bench_launcher_fails_when_a_rank_fails():
     r = _bench(["--gpus", "2", "--workload", "stub"], {"HM_BENCH_STUB_FAIL_RANK": "1"})
     assert r.returncode != 0 and "rank 1 failed" in r.stderr
