@@ -55,6 +55,7 @@ _SIGS = {
     "hm_hash_evaluator": (_i, [_vp, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hm_net_create": (_i, [_vp, _sz, _vp, _vp, C.POINTER(_vp)]),
     "hm_net_create_host": (_i, [_vp, _sz, _vp, _sz, _vp, _sz, C.POINTER(_vp)]),
+    "hm_net_create_w8": (_i, [_vp, _sz, _vp, _vp, _vp, C.POINTER(_vp)]),
     "hm_net_destroy": (_i, [_vp]),
     "hm_net_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hm_net_forward_groups": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -29,6 +29,8 @@
 int hm_fail(int code, const std::string& msg);
 
 #include "hm_net_device.hpp"
+#include "hm_net_w8_device.hpp"    // NetDescW8: the descriptor of a network with FP8 (e4m3) weights
+#include "hm_net_w8.hpp"
 
 namespace hmn {
 
@@ -329,6 +331,8 @@ struct hm_net {
     size_t ldsNarrow = 0;
     int maxBlocks = 1024;
     int wideRows = 256;                      // batches up to this many rows (one workgroup per CU) run the OCC = 1 instantiation
+    bool w8 = false;                         // FP8-weight network (hm_net_create_w8): `nd` is unused, every launch goes to rise_forward_w8
+    hmn::W8Launch w8a;
 };
 
 template <typename K>
@@ -463,6 +467,60 @@ int hm_net_create_host(const int32_t* desc, size_t desc_ints, const void* h_wh, 
     (*out)->owned[0] = dh; (*out)->owned[1] = df;
     return 0;
 }
+// As hm_net_create for a network whose GEMM weights are FP8 (OCP e4m3) codes with one fp32 scale per output channel — the
+// reduced-precision plan the reference builds with TensorRT (nn/engine.cc:290-401, its FP16 builder flag), here weight-only.
+// desc: hmn::NetDescW8 as a flat int32 array (hivemind_amd/net.py FusedNet(weights="fp8")); d_w8: the codes in fragment-pair
+// order; d_wh: the fp16 parameters that stay (stem, depthwise, ECA, value linear); d_wf: biases and scales.  Device buffers,
+// caller-owned.  Such a handle runs through hm_net_forward[_groups[_timed]] / hm_net_profile; hm_net_can_serve is 0 for it.
+int hm_net_create_w8(const int32_t* desc, size_t desc_ints, const void* d_w8, const void* d_wh, const void* d_wf, hm_net** out) {
+    using namespace hmn;
+    if (!desc || !d_w8 || !d_wh || !d_wf || !out) return hm_fail(HM_ERR_INVALID, "null argument");
+    if (desc_ints * 4 != sizeof(NetDescW8)) return hm_fail(HM_ERR_INVALID, "bad fp8 network descriptor size");
+    if ((reinterpret_cast<uintptr_t>(d_w8) & 15) || (reinterpret_cast<uintptr_t>(d_wh) & 15)) return hm_fail(HM_ERR_INVALID, "parameter buffers must be 16-byte aligned");
+    NetDescW8 nd;
+    memcpy(&nd, desc, sizeof(NetDescW8));
+    auto bad = [&](const char* m) { return hm_fail(HM_ERR_INVALID, m); };
+    if (nd.C != 64 && nd.C != 128 && nd.C != 384) return bad("fp8 weights: trunk width must be 64, 128 or 384");
+    if (nd.cin_pad != 80) return bad("fp8 weights: input planes must be padded to 80");
+    if (nd.nblocks > MAXB || nd.nblocks < 0 || nd.cv > 32 || nd.cv < 1) return bad("unsupported network geometry");
+    if ((nd.ps_w | nd.pp_w | nd.v_w) & 1023) return bad("fp8 weights: matrix offsets must be multiples of 1024 bytes");
+    bool k5 = false;
+    int copMax = 32;
+    for (int i = 0; i < nd.nblocks; ++i) {
+        const BlockDescW8& b = nd.blk[i];
+        if (b.k != 3 && b.k != 5) return bad("depthwise kernel must be 3 or 5");
+        if (b.cop <= 0 || b.cop % 32) return bad("fp8 weights: expanded channels must be a positive multiple of 32");
+        if ((b.w1 | b.w2) & 1023) return bad("fp8 weights: matrix offsets must be multiples of 1024 bytes");
+        k5 |= b.k == 5;
+        copMax = std::max(copMax, b.cop);
+    }
+    // LDS plan and chunking rule of the narrow fp16 forms; the chunk's expand scales live in the first 4C floats of the ECA scratch
+    const size_t ldx = nd.C + 8, ldi = nd.cin_pad + 8;
+    auto bytes_for = [&](int cm) {
+        size_t u = std::max((size_t)cm * 66 + (size_t)64 * (cm + 8), (size_t)65 * std::max(ldx, ldi));
+        u = (u + 7) & ~(size_t)7;
+        return std::make_pair(u, (65 * ldx + u) * 2 + (2 * (size_t)cm + nd.C) * 4 + ((((size_t)cm * 25 + 7) & ~(size_t)7) * 2) + (5 * (size_t)nd.C + 64) * 4);
+    };
+    if (const char* ce = std::getenv("HM_NET_COP_CHUNK")) copMax = std::max(64, std::atoi(ce) & ~63);
+    if (copMax > 4 * nd.C) copMax = 4 * nd.C;
+    while (copMax > 64 && bytes_for(copMax).second > 160 * 1024) copMax -= 64;
+    const auto ub = bytes_for(copMax);
+    if (ub.second > 160 * 1024) return bad("network too wide for one LDS tile");
+    hm_net* net = new hm_net();
+    net->w8 = true; net->k5 = k5;
+    if (const char* e = std::getenv("HM_NET_MAX_BLOCKS")) net->maxBlocks = std::atoi(e) > 0 ? std::atoi(e) : 1024;
+    void* dnd = nullptr;
+    if (hipMalloc(&dnd, sizeof(NetDescW8)) != hipSuccess) { delete net; return hm_fail(HM_ERR_NO_DEVICE, "hipMalloc failed"); }
+    hipError_t e = hipMemcpy(dnd, &nd, sizeof(NetDescW8), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = w8_set_lds(nd.C, k5, ub.second);
+    if (e != hipSuccess) { (void)hipFree(dnd); delete net; return hm_fail(HM_ERR_NO_DEVICE, std::string("hm_net_create_w8: ") + hipGetErrorString(e)); }
+    net->owned[0] = dnd;
+    W8Launch& a = net->w8a;
+    a.d_nd = dnd; a.d_w8 = d_w8; a.d_wh = d_wh; a.d_wf = d_wf;
+    a.C = nd.C; a.k5 = k5; a.copMax = copMax; a.uHalfs = (int)ub.first; a.ldsBytes = ub.second;
+    *out = net;
+    return 0;
+}
 int hm_net_destroy(hm_net* net) {
     if (!net) return 0;
     if (net->d_nd) (void)hipFree(net->d_nd);
@@ -478,7 +536,9 @@ static int net_forward_impl(const hm_net* net, const void* d_planes, int n, cons
     if (d_group_rows && group <= 0) return hm_fail(HM_ERR_INVALID, "group size must be positive");
     const int grid = n < net->maxBlocks ? n : net->maxBlocks;
     const bool wide = n <= net->wideRows;           // small batches: one workgroup per CU, full register file
-    const hipError_t e = net->narrow
+    const hipError_t e = net->w8
+        ? hmn::w8_launch(net->w8a, grid, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_dbg, d_clk)
+        : net->narrow
         ? with_narrow(net, [&](auto kern) {
               return launch_narrow(kern, net, grid, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_dbg, d_clk);
           })

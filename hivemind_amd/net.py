@@ -293,20 +293,57 @@ def _pack_frag(wt: torch.Tensor) -> torch.Tensor:
     return x.permute(0, 3, 1, 4, 2).contiguous().reshape(-1)   # ks, t, h, c, j
 
 
+def quantize_e4m3(w2d: torch.Tensor):
+    """[K, N] fp32 (GEMM orientation) -> (codes uint8 [K, N], scale fp32 [N]): OCP e4m3 with one scale per output channel,
+    scale[n] = amax_k |w[k, n]| / 448 (448 = the largest e4m3 value, so no code saturates to the NaN pattern).  An all-zero
+    column gets scale 1.0 and zero codes."""
+    w2d = w2d.detach().float()
+    amax = w2d.abs().amax(dim=0)
+    scale = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    q = (w2d / scale).clamp(-448.0, 448.0)                # fp32 division may land a hair over 448
+    codes = q.to(torch.float8_e4m3fn).view(torch.uint8)
+    assert not bool(((codes & 0x7F) == 0x7F).any()), "e4m3 NaN code"
+    return codes.contiguous(), scale.contiguous()
+
+
+def _pack_frag8(codes: torch.Tensor) -> torch.Tensor:
+    """[K, N] bytes (K % 32 == 0, N % 32 == 0) -> the fragment order of _pack_frag with two k-steps per lane,
+    [kstep/2][tile][lane][2][8]: lane l holds, for k-steps ks = 2p and 2p + 1, W[ks*16 + 8*(l>>5) + j][tile*32 + (l&31)]
+    (16 bytes per lane, one coalesced 1 KiB wave-load per k-step pair)."""
+    k, n = codes.shape
+    assert k % 32 == 0 and n % 32 == 0, (k, n)
+    x = codes.reshape(k // 32, 2, 2, 8, n // 32, 32)     # p, u (k-step of the pair), h, j, t, c
+    return x.permute(0, 4, 2, 5, 1, 3).contiguous().reshape(-1)   # p, t, h, c, u, j
+
+
 class FusedNet:
-    """RiseV3 (eval) -> one hm_net_forward launch per batch.  Same output contract as InferenceNet."""
+    """RiseV3 (eval) -> one hm_net_forward launch per batch.  Same output contract as InferenceNet.
+    weights="fp8": the 1x1 expand / project, policy-trunk, policy-projection and value convolutions are stored and fetched as
+    e4m3 codes with one fp32 scale per output channel (quantize_e4m3 after BatchNorm folding; hm_net_create_w8); activations stay
+    fp16, accumulation fp32.  Such a network runs through the same calls; it has no plan file (save) yet."""
 
     MAXB, CIN_PAD = 16, 80
 
-    def __init__(self, model: RiseV3, device="cuda"):
+    def __init__(self, model: RiseV3, device="cuda", weights="fp16"):
         import ctypes as C
         import numpy as np
         from ._lib import lib, check
         import copy
+        if weights not in ("fp16", "fp8"):
+            raise ValueError("weights must be 'fp16' or 'fp8'")
+        self.weights = weights
+        fp8 = weights == "fp8"
         self._C, self._lib, self._check = C, lib, check
         model = copy.deepcopy(model).cpu().float().eval()       # packing happens on the host
-        halfs, floats = [], []
-        hoff, foff = [0], [0]
+        halfs, floats, bytes8 = [], [], []
+        hoff, foff, boff = [0], [0], [0]
+
+        def addq(wt):          # fp8: [K, N] -> (byte offset of the packed codes, float offset of the scales)
+            codes, scale = quantize_e4m3(wt)
+            off = boff[0]
+            bytes8.append(_pack_frag8(codes))
+            boff[0] += codes.numel()
+            return off, addf(scale)
 
         def addh(t):
             t = t.detach().float().reshape(-1)
@@ -351,11 +388,17 @@ class FusedNet:
             cop, k = w1.shape[0], wd.shape[-1]
             assert cop % 32 == 0 and k in (3, 5)
             d = dict(cop=cop, k=k, eca=0, ecaw=0, ecab=0)
-            d["w1"] = addh(_pack_frag(w1.reshape(cop, ch).t().contiguous()))
+            if fp8:
+                d["w1"], d["s1"] = addq(w1.reshape(cop, ch).t().contiguous())
+            else:
+                d["w1"] = addh(_pack_frag(w1.reshape(cop, ch).t().contiguous()))
             d["b1"] = addf(b1)
             d["dw"] = addh(wd.reshape(cop, k * k))
             d["b2"] = addf(b2)
-            d["w2"] = addh(_pack_frag(w2.reshape(ch, cop).t().contiguous()))
+            if fp8:
+                d["w2"], d["s3"] = addq(w2.reshape(ch, cop).t().contiguous())
+            else:
+                d["w2"] = addh(_pack_frag(w2.reshape(ch, cop).t().contiguous()))
             d["b3"] = addf(b3)
             if blk.se_type:
                 c1 = blk.se.body[0]
@@ -370,15 +413,25 @@ class FusedNet:
         cv = wv.shape[0]
         assert cv <= 32
         desc["cv"] = cv
-        desc["v_w"] = addh(_pack_frag(padn(wv.reshape(cv, ch).t().contiguous(), 32)))
+        if fp8:
+            desc["v_w"], desc["v_s"] = addq(padn(wv.reshape(cv, ch).t().contiguous(), 32))
+        else:
+            desc["v_w"] = addh(_pack_frag(padn(wv.reshape(cv, ch).t().contiguous(), 32)))
         desc["v_b"] = addf(torch.cat([bv, torch.zeros(32 - cv)]))
         desc["vl_w"] = addh(torch.cat([vh.body_wdl[0].weight, vh.body_plys[0].weight], 0))
         desc["vl_b"] = addf(torch.cat([vh.body_wdl[0].bias, vh.body_plys[0].bias]))
         ph = model.policy_heads
         ws, bs = _fold(ph.shared_body[0], ph.shared_body[1])
-        desc["ps_w"] = addh(_pack_frag(conv3_wt(ws)))
+        if fp8:
+            desc["ps_w"], desc["ps_s"] = addq(conv3_wt(ws))
+        else:
+            desc["ps_w"] = addh(_pack_frag(conv3_wt(ws)))
         desc["ps_b"] = addf(bs)
         wp = torch.cat([ph.board_projections[0].weight.detach().float(), ph.board_projections[1].weight.detach().float()], 0)
+        if fp8:
+            desc["pp_w"], desc["pp_s"] = addq(padn(conv3_wt(wp), 160))
+            self._init_w8(desc, blocks, halfs, floats, bytes8, device)
+            return
         desc["pp_w"] = addh(_pack_frag(padn(conv3_wt(wp), 160)))
         ints = [desc["C"], len(blocks), desc["cv"], desc["cin_pad"], desc["stem_w"], desc["ps_w"], desc["pp_w"], desc["v_w"],
                 desc["vl_w"], desc["stem_b"], desc["ps_b"], desc["v_b"], desc["vl_b"]]
@@ -397,6 +450,28 @@ class FusedNet:
         check(lib.hm_net_create(self.desc.ctypes.data, self.desc.size, self.wh.data_ptr(), self.wf.data_ptr(), C.byref(h)))
         self.handle = h            # hm_net*: descriptor on the device, launch geometry resolved once
 
+    def _init_w8(self, desc, blocks, halfs, floats, bytes8, device):
+        """The fp8 network's descriptor (hmn::NetDescW8, hm_net_w8_device.hpp) and its three parameter buffers."""
+        import numpy as np
+        C = self._C
+        ints = [desc["C"], len(blocks), desc["cv"], desc["cin_pad"], desc["stem_w"], desc["vl_w"], desc["ps_w"], desc["pp_w"], desc["v_w"],
+                desc["stem_b"], desc["ps_b"], desc["v_b"], desc["vl_b"], desc["ps_s"], desc["pp_s"], desc["v_s"]]
+        for i in range(self.MAXB):
+            if i < len(blocks):
+                d = blocks[i]
+                ints += [d["cop"], d["k"], d["eca"], 0, d["w1"], d["w2"], d["dw"], d["ecaw"], d["b1"], d["b2"], d["b3"], d["ecab"], d["s1"], d["s3"]]
+            else:
+                ints += [0] * 14
+        self.desc = np.asarray(ints, dtype=np.int32)
+        self.w8 = torch.cat(bytes8).to(device=device).contiguous()
+        self.wh = torch.cat(halfs).to(device=device, dtype=torch.float16).contiguous()
+        self.wf = torch.cat(floats).to(device=device, dtype=torch.float32).contiguous()
+        self.device = self.wh.device
+        self._out = {}
+        h = C.c_void_p()
+        self._check(self._lib.hm_net_create_w8(self.desc.ctypes.data, self.desc.size, self.w8.data_ptr(), self.wh.data_ptr(), self.wf.data_ptr(), C.byref(h)))
+        self.handle = h
+
     def close(self):
         if getattr(self, "handle", None):
             self._lib.hm_net_destroy(self.handle)
@@ -410,6 +485,8 @@ class FusedNet:
 
     def save(self, path: str):
         """Packed-network file (the plan-file counterpart Engine::loadNetwork reads back, nn/engine.cc:290-401)."""
+        if self.weights != "fp16":
+            raise NotImplementedError("plan files hold fp16 networks only")
         wh = self.wh.cpu().numpy()
         wf = self.wf.cpu().numpy()
         self._check(self._lib.hm_net_save_file(str(path).encode(), self.desc.ctypes.data, self.desc.size, wh.ctypes.data, wh.nbytes,

@@ -341,6 +341,13 @@ int hm_sp_trace(unsigned long long* out, int cap);
 typedef struct hm_net hm_net;
 int hm_net_create(const int32_t* desc, size_t desc_ints, const void* d_wh, const void* d_wf, hm_net** out);
 int hm_net_create_host(const int32_t* desc, size_t desc_ints, const void* h_wh, size_t wh_bytes, const void* h_wf, size_t wf_bytes, hm_net** out);
+/* The same network with FP8 weights (the reduced-precision plan of nn/engine.cc:290-401, weight-only): the 1x1 expand /
+ * project, policy-trunk, policy-projection and value convolutions as OCP e4m3 codes with one fp32 scale per output channel
+ * (d_w8, fragment-pair order; scales in d_wf), everything else fp16 / fp32 as above; desc = hmn::NetDescW8 as int32s
+ * (net.py FusedNet(weights="fp8")).  Trunks of 64 / 128 / 384 channels, input planes padded to 80.  The handle serves
+ * hm_net_forward, hm_net_forward_groups[_timed], hm_net_profile and hm_net_destroy; it cannot be the evaluator of
+ * hm_sp_search (the self-play driver then takes its host-driven loop). */
+int hm_net_create_w8(const int32_t* desc, size_t desc_ints, const void* d_w8, const void* d_wh, const void* d_wf, hm_net** out);
 int hm_net_destroy(hm_net* net);
 int hm_net_forward(const hm_net* net, const void* d_planes, int n,
                    void* d_value, void* d_pi_a, void* d_pi_b, void* d_wdl, void* d_moves_left, void* stream);

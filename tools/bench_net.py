@@ -1,27 +1,67 @@
-import sys, os, time, json
+"""Stand-alone timing of the fused forward.  Default: the fused HIP forward against the graph-replayed torch form.
+--weights fp8: the fp8-weight form against the two fp16 forms (4-wave: HM_NET_WAVES=4, 8-wave default) in one process, the forms
+alternated round by round, device events over >= 20 launches each; writes ms per launch, TFLOP/s and the weight bytes a position
+streams (computed from the packed buffers' shapes) to --out."""
+import argparse, sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, hivemind_amd as hm
 from hivemind_amd import net as N
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--weights", choices=("fp16", "fp8"), default="fp16")
+ap.add_argument("--rows", type=int, nargs="+", default=None)
+ap.add_argument("--rounds", type=int, default=4)
+ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--out", default="net_fp8.json")
+args = ap.parse_args()
 hm.init(0)
 torch.manual_seed(0)
 out = {}
+
+
+def timed(f, x, iters):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(iters): f(x)
+    e.record(); torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters
+
+
 for name, mk in (("small", N.rise_v3_small), ("full", N.rise_v33)):
     model = mk()
     fl = N.flops_per_position(model)
+    if args.weights == "fp8":
+        forms = {}
+        for label, waves, w in (("fp8_w4", None, "fp8"), ("fp16_w4", "4", "fp16"), ("fp16_w8", "8", "fp16")):
+            if waves: os.environ["HM_NET_WAVES"] = waves              # read once, by hm_net_create
+            forms[label] = N.FusedNet(model, weights=w)
+        os.environ.pop("HM_NET_WAVES", None)
+        wbytes = {k: int(f.wh.numel() * 2 + (f.w8.numel() if f.weights == "fp8" else 0)) for k, f in forms.items()}
+        for n in args.rows or (64, 512, 2048):
+            x = torch.rand((n, 74, 8, 8), device="cuda").half()
+            for f in forms.values():
+                for _ in range(3): f(x)
+            torch.cuda.synchronize()
+            ms = {k: [] for k in forms}
+            for _ in range(args.rounds):                              # alternate the forms: drift hits all of them alike
+                for k, f in forms.items(): ms[k].append(timed(f, x, args.iters))
+            res = {k: dict(ms=sum(v) / len(v), ms_min=min(v), ms_max=max(v), launches=len(v) * args.iters,
+                           tflops=n * fl / (sum(v) / len(v) * 1e-3) / 1e12, weight_bytes_per_position=wbytes[k]) for k, v in ms.items()}
+            out[f"{name}_{n}"] = res
+            print(name, n, json.dumps(res), flush=True)
+        continue
     fused = N.FusedNet(model)
-    for n in (64, 512, 2048, 8192):
+    for n in args.rows or (64, 512, 2048, 8192):
         x = torch.rand((n, 74, 8, 8), device="cuda").half()
         inf = N.InferenceNet(model).capture(n)
         res = {}
         for label, f in (("fused", fused), ("torch_graph", inf)):
             for _ in range(3): f(x)
             torch.cuda.synchronize()
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            iters = 20
-            s.record()
-            for _ in range(iters): f(x)
-            e.record(); torch.cuda.synchronize()
-            ms = s.elapsed_time(e) / iters
+            ms = timed(f, x, 20)
             res[label] = dict(ms=ms, tflops=n * fl / (ms * 1e-3) / 1e12)
         out[f"{name}_{n}"] = res
         print(name, n, json.dumps(res), flush=True)
+if args.weights == "fp8":
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    json.dump(out, open(args.out, "w"), indent=1)
