@@ -31,6 +31,7 @@ int hm_fail(int code, const std::string& msg);
 #include "hm_net_device.hpp"
 #include "hm_net_w8_device.hpp"    // NetDescW8: the descriptor of a network with FP8 (e4m3) weights
 #include "hm_net_w8.hpp"
+#include "hm_net_pair.hpp"      // the pair form (two positions per workgroup): hm_net_set_pair
 
 namespace hmn {
 
@@ -333,6 +334,8 @@ struct hm_net {
     int wideRows = 256;                      // batches up to this many rows (one workgroup per CU) run the OCC = 1 instantiation
     bool w8 = false;                         // FP8-weight network (hm_net_create_w8): `nd` is unused, every launch goes to rise_forward_w8
     hmn::W8Launch w8a;
+    bool pair = false;                       // pair form selected (hm_net_set_pair): every launch goes to rise_forward_pair
+    hmn::PairLaunch pa;
 };
 
 template <typename K>
@@ -521,6 +524,28 @@ int hm_net_create_w8(const int32_t* desc, size_t desc_ints, const void* d_w8, co
     *out = net;
     return 0;
 }
+// Selects (on != 0) or leaves (on == 0) the pair form for this handle: two positions per 4-wave workgroup, every weight fragment
+// multiplying M = 128 rows (hm_net_pair.hip).  fp16 narrow trunks of 64 or 128 channels; results are bit-identical to the other forms.
+int hm_net_set_pair(hm_net* net, int on) {
+    if (!net) return hm_fail(HM_ERR_INVALID, "null argument");
+    if (!on) { net->pair = false; return 0; }
+    if (net->w8) return hm_fail(HM_ERR_INVALID, "pair form: fp8-weight networks are not supported");
+    if (!net->narrow) return hm_fail(HM_ERR_INVALID, "pair form: the network does not run the narrow forward");
+    if (net->nd.C != 64 && net->nd.C != 128)
+        return hm_fail(HM_ERR_INVALID, "pair form: trunk width must be 64 or 128 (two activation and two policy-trunk tiles of a 384-channel trunk exceed one CU's LDS)");
+    hmn::PairLaunch a;
+    int maxCop = 32;
+    for (int i = 0; i < net->nd.nblocks; ++i) {
+        if (net->nd.blk[i].cop <= 0 || net->nd.blk[i].cop % 32) return hm_fail(HM_ERR_INVALID, "pair form: expanded channels must be a positive multiple of 32");
+        maxCop = std::max(maxCop, net->nd.blk[i].cop);
+    }
+    if (!hmn::pair_plan(net->nd.C, net->nd.cin_pad, maxCop, a)) return hm_fail(HM_ERR_INVALID, "pair form: two positions do not fit one CU's LDS");
+    a.d_nd = net->d_nd; a.d_wh = net->d_wh; a.d_wf = net->d_wf; a.k5 = net->k5;
+    const hipError_t e = hmn::pair_set_lds(a);
+    if (e != hipSuccess) return hm_fail(HM_ERR_NO_DEVICE, std::string("hm_net_set_pair: ") + hipGetErrorString(e));
+    net->pa = a; net->pair = true;
+    return 0;
+}
 int hm_net_destroy(hm_net* net) {
     if (!net) return 0;
     if (net->d_nd) (void)hipFree(net->d_nd);
@@ -538,6 +563,8 @@ static int net_forward_impl(const hm_net* net, const void* d_planes, int n, cons
     const bool wide = n <= net->wideRows;           // small batches: one workgroup per CU, full register file
     const hipError_t e = net->w8
         ? hmn::w8_launch(net->w8a, grid, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_dbg, d_clk)
+        : net->pair
+        ? hmn::pair_launch(net->pa, net->maxBlocks, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_dbg, d_clk)
         : net->narrow
         ? with_narrow(net, [&](auto kern) {
               return launch_narrow(kern, net, grid, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_dbg, d_clk);

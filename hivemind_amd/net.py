@@ -320,18 +320,22 @@ class FusedNet:
     """RiseV3 (eval) -> one hm_net_forward launch per batch.  Same output contract as InferenceNet.
     weights="fp8": the 1x1 expand / project, policy-trunk, policy-projection and value convolutions are stored and fetched as
     e4m3 codes with one fp32 scale per output channel (quantize_e4m3 after BatchNorm folding; hm_net_create_w8); activations stay
-    fp16, accumulation fp32.  Such a network runs through the same calls; it has no plan file (save) yet."""
+    fp16, accumulation fp32.  Such a network runs through the same calls; it has no plan file (save) yet.
+    pair=True: the pair form of the forward (hm_net_set_pair: two positions per workgroup, every weight fragment multiplying
+    M = 128 rows; fp16 trunks of 64 / 128 channels).  Same results bit for bit; the plan file does not record the form."""
 
     MAXB, CIN_PAD = 16, 80
 
-    def __init__(self, model: RiseV3, device="cuda", weights="fp16"):
+    def __init__(self, model: RiseV3, device="cuda", weights="fp16", pair=False):
         import ctypes as C
         import numpy as np
         from ._lib import lib, check
         import copy
         if weights not in ("fp16", "fp8"):
             raise ValueError("weights must be 'fp16' or 'fp8'")
-        self.weights = weights
+        if pair and weights == "fp8":
+            raise ValueError("pair=True needs fp16 weights")
+        self.weights, self.pair = weights, bool(pair)
         fp8 = weights == "fp8"
         self._C, self._lib, self._check = C, lib, check
         model = copy.deepcopy(model).cpu().float().eval()       # packing happens on the host
@@ -449,6 +453,8 @@ class FusedNet:
         h = C.c_void_p()
         check(lib.hm_net_create(self.desc.ctypes.data, self.desc.size, self.wh.data_ptr(), self.wf.data_ptr(), C.byref(h)))
         self.handle = h            # hm_net*: descriptor on the device, launch geometry resolved once
+        if self.pair:
+            check(lib.hm_net_set_pair(h, 1))
 
     def _init_w8(self, desc, blocks, halfs, floats, bytes8, device):
         """The fp8 network's descriptor (hmn::NetDescW8, hm_net_w8_device.hpp) and its three parameter buffers."""

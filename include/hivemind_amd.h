@@ -348,6 +348,12 @@ int hm_net_create_host(const int32_t* desc, size_t desc_ints, const void* h_wh, 
  * hm_net_forward, hm_net_forward_groups[_timed], hm_net_profile and hm_net_destroy; it cannot be the evaluator of
  * hm_sp_search (the self-play driver then takes its host-driven loop). */
 int hm_net_create_w8(const int32_t* desc, size_t desc_ints, const void* d_w8, const void* d_wh, const void* d_wf, hm_net** out);
+/* The pair form of the forward for this handle: on != 0 makes hm_net_forward, hm_net_forward_groups[_timed] and hm_net_profile
+ * run two positions (rows 2p, 2p + 1) per 4-wave workgroup, every weight fragment multiplying M = 128 rows; on == 0 restores the
+ * previous form.  Results are bit-identical to the other forms, rows outside a group's count stay untouched.  fp16 trunks of 64 or
+ * 128 channels; HM_ERR_INVALID for an fp8-weight network, a network without the narrow forward and the 384-channel trunk.
+ * hm_net_can_serve / hm_net_serve_info_get are unaffected (the single-launch search keeps its one-position evaluator). */
+int hm_net_set_pair(hm_net* net, int on);
 int hm_net_destroy(hm_net* net);
 int hm_net_forward(const hm_net* net, const void* d_planes, int n,
                    void* d_value, void* d_pi_a, void* d_pi_b, void* d_wdl, void* d_moves_left, void* stream);

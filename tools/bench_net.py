@@ -1,7 +1,9 @@
 """Stand-alone timing of the fused forward.  Default: the fused HIP forward against the graph-replayed torch form.
 --weights fp8: the fp8-weight form against the two fp16 forms (4-wave: HM_NET_WAVES=4, 8-wave default) in one process, the forms
 alternated round by round, device events over >= 20 launches each; writes ms per launch, TFLOP/s and the weight bytes a position
-streams (computed from the packed buffers' shapes) to --out."""
+streams (computed from the packed buffers' shapes) to --out.
+--pair: the same alternation for the pair form (two positions per workgroup) of RISEv3-small against the two fp16 forms; the
+384-channel network, which has no pair form, is left out."""
 import argparse, sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, hivemind_amd as hm
@@ -9,11 +11,14 @@ from hivemind_amd import net as N
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--weights", choices=("fp16", "fp8"), default="fp16")
+ap.add_argument("--pair", action="store_true")
 ap.add_argument("--rows", type=int, nargs="+", default=None)
 ap.add_argument("--rounds", type=int, default=4)
 ap.add_argument("--iters", type=int, default=10)
-ap.add_argument("--out", default="net_fp8.json")
+ap.add_argument("--out", default=None)
 args = ap.parse_args()
+alternate = args.pair or args.weights == "fp8"
+if args.out is None: args.out = "net_pair.json" if args.pair else "net_fp8.json"
 hm.init(0)
 torch.manual_seed(0)
 out = {}
@@ -27,14 +32,15 @@ def timed(f, x, iters):
     return s.elapsed_time(e) / iters
 
 
-for name, mk in (("small", N.rise_v3_small), ("full", N.rise_v33)):
+for name, mk in (("small", N.rise_v3_small), ("full", N.rise_v33))[:1 if args.pair else 2]:
     model = mk()
     fl = N.flops_per_position(model)
-    if args.weights == "fp8":
+    if alternate:
         forms = {}
-        for label, waves, w in (("fp8_w4", None, "fp8"), ("fp16_w4", "4", "fp16"), ("fp16_w8", "8", "fp16")):
+        first = ("pair", None, "fp16") if args.pair else ("fp8_w4", None, "fp8")
+        for label, waves, w in (first, ("fp16_w4", "4", "fp16"), ("fp16_w8", "8", "fp16")):
             if waves: os.environ["HM_NET_WAVES"] = waves              # read once, by hm_net_create
-            forms[label] = N.FusedNet(model, weights=w)
+            forms[label] = N.FusedNet(model, weights=w, pair=label == "pair")
         os.environ.pop("HM_NET_WAVES", None)
         wbytes = {k: int(f.wh.numel() * 2 + (f.w8.numel() if f.weights == "fp8" else 0)) for k, f in forms.items()}
         for n in args.rows or (64, 512, 2048):
@@ -62,6 +68,6 @@ for name, mk in (("small", N.rise_v3_small), ("full", N.rise_v33)):
             res[label] = dict(ms=ms, tflops=n * fl / (ms * 1e-3) / 1e12)
         out[f"{name}_{n}"] = res
         print(name, n, json.dumps(res), flush=True)
-if args.weights == "fp8":
+if alternate:
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     json.dump(out, open(args.out, "w"), indent=1)
