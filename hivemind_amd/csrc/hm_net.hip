@@ -32,6 +32,7 @@ int hm_fail(int code, const std::string& msg);
 #include "hm_net_w8_device.hpp"    // NetDescW8: the descriptor of a network with FP8 (e4m3) weights
 #include "hm_net_w8.hpp"
 #include "hm_net_pair.hpp"      // the pair form (two positions per workgroup): hm_net_set_pair
+#include "hm_net_split.hpp"     // the team form (one position over 2 or 3 workgroups): hm_net_set_split
 
 namespace hmn {
 
@@ -336,6 +337,8 @@ struct hm_net {
     hmn::W8Launch w8a;
     bool pair = false;                       // pair form selected (hm_net_set_pair): every launch goes to rise_forward_pair
     hmn::PairLaunch pa;
+    int split = 0;                           // team form selected (hm_net_set_split): 2 or 3 workgroups per position, every launch goes to rise_forward_split
+    hmn::SplitLaunch sa;                     // its workspace is allocated by the first hm_net_set_split and freed by hm_net_destroy
 };
 
 template <typename K>
@@ -530,6 +533,7 @@ int hm_net_set_pair(hm_net* net, int on) {
     if (!net) return hm_fail(HM_ERR_INVALID, "null argument");
     if (!on) { net->pair = false; return 0; }
     if (net->w8) return hm_fail(HM_ERR_INVALID, "pair form: fp8-weight networks are not supported");
+    if (net->split) return hm_fail(HM_ERR_INVALID, "pair form: the handle is in team form (hm_net_set_split)");
     if (!net->narrow) return hm_fail(HM_ERR_INVALID, "pair form: the network does not run the narrow forward");
     if (net->nd.C != 64 && net->nd.C != 128)
         return hm_fail(HM_ERR_INVALID, "pair form: trunk width must be 64 or 128 (two activation and two policy-trunk tiles of a 384-channel trunk exceed one CU's LDS)");
@@ -546,8 +550,44 @@ int hm_net_set_pair(hm_net* net, int on) {
     net->pa = a; net->pair = true;
     return 0;
 }
+// Selects the team form for this handle: t = 2 or 3 workgroups carry one position of the 384-channel trunk through one launch, each
+// streaming about 1/t of every weight matrix (hm_net_split.hip); t = 0 leaves it.  Results are bit-identical to the other forms.
+int hm_net_set_split(hm_net* net, int t) {
+    if (!net) return hm_fail(HM_ERR_INVALID, "null argument");
+    if (t == 0) { net->split = 0; return 0; }
+    if (t != 2 && t != 3) return hm_fail(HM_ERR_INVALID, "team form: the team size must be 2 or 3");
+    if (net->w8) return hm_fail(HM_ERR_INVALID, "team form: fp8-weight networks are not supported");
+    if (net->pair) return hm_fail(HM_ERR_INVALID, "team form: the handle is in pair form (hm_net_set_pair)");
+    if (!net->narrow || net->nd.C != 384) return hm_fail(HM_ERR_INVALID, "team form: the trunk must have 384 channels (narrower trunks leave a member fewer tiles than waves)");
+    if (net->split == t) return 0;
+    int maxCop = 32;
+    for (int i = 0; i < net->nd.nblocks; ++i) {
+        if (net->nd.blk[i].cop <= 0 || net->nd.blk[i].cop % 32) return hm_fail(HM_ERR_INVALID, "team form: expanded channels must be a positive multiple of 32");
+        maxCop = std::max(maxCop, net->nd.blk[i].cop);
+    }
+    if (net->nd.cv < 1) return hm_fail(HM_ERR_INVALID, "team form: unsupported network geometry");
+    net->split = 0;
+    hmn::split_release(net->sa);             // another team size: another number of teams
+    hmn::SplitLaunch a;
+    a.d_nd = net->d_nd; a.d_wh = net->d_wh; a.d_wf = net->d_wf; a.k5 = net->k5; a.T = t;
+    const hipError_t e = hmn::split_prepare(a, maxCop, net->maxBlocks);
+    if (e == hipErrorInvalidValue) return hm_fail(HM_ERR_INVALID, "team form: not even one team is resident together (HM_NET_MAX_BLOCKS below the team size?)");
+    if (e != hipSuccess) return hm_fail(HM_ERR_NO_DEVICE, std::string("hm_net_set_split: ") + hipGetErrorString(e));
+    net->sa = a; net->split = t;
+    return 0;
+}
+// Blocking read of a team-form handle's error word: *code = 0 when no launch has given up, else the code of the first give-up
+// (1: a partner never arrived, 2: a later wait ran out); a set word is cleared, together with the teams' counters.
+int hm_net_split_error(const hm_net* net, int* code) {
+    if (!net || !code) return hm_fail(HM_ERR_INVALID, "null argument");
+    if (!net->sa.ws) return hm_fail(HM_ERR_INVALID, "the handle has never been in team form");
+    const hipError_t e = hmn::split_take_error(net->sa, code);
+    if (e != hipSuccess) return hm_fail(HM_ERR_NO_DEVICE, std::string("hm_net_split_error: ") + hipGetErrorString(e));
+    return 0;
+}
 int hm_net_destroy(hm_net* net) {
     if (!net) return 0;
+    hmn::split_release(net->sa);
     if (net->d_nd) (void)hipFree(net->d_nd);
     for (void* p : net->owned) if (p) (void)hipFree(p);
     delete net;
@@ -563,6 +603,8 @@ static int net_forward_impl(const hm_net* net, const void* d_planes, int n, cons
     const bool wide = n <= net->wideRows;           // small batches: one workgroup per CU, full register file
     const hipError_t e = net->w8
         ? hmn::w8_launch(net->w8a, grid, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_dbg, d_clk)
+        : net->split
+        ? hmn::split_launch(net->sa, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_clk)
         : net->pair
         ? hmn::pair_launch(net->pa, net->maxBlocks, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_dbg, d_clk)
         : net->narrow

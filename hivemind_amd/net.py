@@ -322,11 +322,14 @@ class FusedNet:
     e4m3 codes with one fp32 scale per output channel (quantize_e4m3 after BatchNorm folding; hm_net_create_w8); activations stay
     fp16, accumulation fp32.  Such a network runs through the same calls; it has no plan file (save) yet.
     pair=True: the pair form of the forward (hm_net_set_pair: two positions per workgroup, every weight fragment multiplying
-    M = 128 rows; fp16 trunks of 64 / 128 channels).  Same results bit for bit; the plan file does not record the form."""
+    M = 128 rows; fp16 trunks of 64 / 128 channels).  Same results bit for bit; the plan file does not record the form.
+    split=2 or 3: the team form (hm_net_set_split: every position of the fp16 384-channel trunk is carried by that many workgroups
+    inside the one launch, each streaming its share of the weights).  Same results bit for bit; launches of team-form networks must
+    not overlap each other (one stream); split_error() tells whether a launch gave up."""
 
     MAXB, CIN_PAD = 16, 80
 
-    def __init__(self, model: RiseV3, device="cuda", weights="fp16", pair=False):
+    def __init__(self, model: RiseV3, device="cuda", weights="fp16", pair=False, split=0):
         import ctypes as C
         import numpy as np
         from ._lib import lib, check
@@ -335,7 +338,9 @@ class FusedNet:
             raise ValueError("weights must be 'fp16' or 'fp8'")
         if pair and weights == "fp8":
             raise ValueError("pair=True needs fp16 weights")
-        self.weights, self.pair = weights, bool(pair)
+        if split and (pair or weights == "fp8"):
+            raise ValueError("split needs fp16 weights and pair=False")
+        self.weights, self.pair, self.split = weights, bool(pair), int(split)
         fp8 = weights == "fp8"
         self._C, self._lib, self._check = C, lib, check
         model = copy.deepcopy(model).cpu().float().eval()       # packing happens on the host
@@ -455,6 +460,14 @@ class FusedNet:
         self.handle = h            # hm_net*: descriptor on the device, launch geometry resolved once
         if self.pair:
             check(lib.hm_net_set_pair(h, 1))
+        if self.split:
+            check(lib.hm_net_set_split(h, self.split))
+
+    def split_error(self) -> int:
+        """Blocking: 0 when no launch of the team form has given up, else the code of the first give-up (cleared by this call)."""
+        code = self._C.c_int(0)
+        self._check(self._lib.hm_net_split_error(self.handle, self._C.byref(code)))
+        return code.value
 
     def _init_w8(self, desc, blocks, halfs, floats, bytes8, device):
         """The fp8 network's descriptor (hmn::NetDescW8, hm_net_w8_device.hpp) and its three parameter buffers."""

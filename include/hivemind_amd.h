@@ -354,6 +354,21 @@ int hm_net_create_w8(const int32_t* desc, size_t desc_ints, const void* d_w8, co
  * 128 channels; HM_ERR_INVALID for an fp8-weight network, a network without the narrow forward and the 384-channel trunk.
  * hm_net_can_serve / hm_net_serve_info_get are unaffected (the single-launch search keeps its one-position evaluator). */
 int hm_net_set_pair(hm_net* net, int on);
+/* The team form of the forward for this handle: t = 2 or 3 makes hm_net_forward and hm_net_forward_groups[_timed] carry every
+ * position over a team of t workgroups inside the one launch, each member streaming about 1/t of every weight matrix and handing
+ * activation slices to its partners through a workspace the handle owns (allocated here, freed by hm_net_destroy); t = 0 restores
+ * the previous form.  Results are bit-identical to the other forms, rows outside a group's count stay untouched.  fp16 trunk of
+ * 384 channels only; HM_ERR_INVALID for another t, another trunk width, an fp8-weight network and a handle in pair form
+ * (hm_net_set_pair in turn refuses a handle in team form).  At most floor(min(resident workgroups, HM_NET_MAX_BLOCKS) / t) teams
+ * are launched, so that every member's partners run with it.  hm_net_can_serve / hm_net_serve_info_get are unaffected.
+ * Contract: launches of one team-form handle, and of two team-form handles on one device, must not overlap each other (one stream,
+ * or ordered by events); kernels that end by themselves may run beside a team-form launch.  Every wait inside the launch is
+ * bounded: a violation, or a team that is not resident together, ends in the handle's error word, not in a hang — the launch then
+ * leaves its outputs unspecified, and later launches of the handle do nothing until hm_net_split_error has been called. */
+int hm_net_set_split(hm_net* net, int t);
+/* Blocking (waits for the device): *code = the error word of a handle that is or has been in team form — 0: no launch gave up;
+ * 1: a member's partners never arrived; 2: a later wait ran out.  A set word is cleared and the teams' counters are reset. */
+int hm_net_split_error(const hm_net* net, int* code);
 int hm_net_destroy(hm_net* net);
 int hm_net_forward(const hm_net* net, const void* d_planes, int n,
                    void* d_value, void* d_pi_a, void* d_pi_b, void* d_wdl, void* d_moves_left, void* stream);

@@ -3,7 +3,9 @@
 alternated round by round, device events over >= 20 launches each; writes ms per launch, TFLOP/s and the weight bytes a position
 streams (computed from the packed buffers' shapes) to --out.
 --pair: the same alternation for the pair form (two positions per workgroup) of RISEv3-small against the two fp16 forms; the
-384-channel network, which has no pair form, is left out."""
+384-channel network, which has no pair form, is left out.
+--split T: the same alternation for the team form (T = 2 or 3 workgroups per position) of the deployed 384-channel network against
+the two fp16 forms, at the row counts of one game's search (8, 16, 64, 128 by default); RISEv3-small has no team form."""
 import argparse, sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, hivemind_amd as hm
@@ -12,13 +14,14 @@ from hivemind_amd import net as N
 ap = argparse.ArgumentParser()
 ap.add_argument("--weights", choices=("fp16", "fp8"), default="fp16")
 ap.add_argument("--pair", action="store_true")
+ap.add_argument("--split", type=int, default=0, choices=(0, 2, 3))
 ap.add_argument("--rows", type=int, nargs="+", default=None)
 ap.add_argument("--rounds", type=int, default=4)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
-alternate = args.pair or args.weights == "fp8"
-if args.out is None: args.out = "net_pair.json" if args.pair else "net_fp8.json"
+alternate = args.pair or args.split or args.weights == "fp8"
+if args.out is None: args.out = "net_pair.json" if args.pair else "net_split.json" if args.split else "net_fp8.json"
 hm.init(0)
 torch.manual_seed(0)
 out = {}
@@ -32,18 +35,18 @@ def timed(f, x, iters):
     return s.elapsed_time(e) / iters
 
 
-for name, mk in (("small", N.rise_v3_small), ("full", N.rise_v33))[:1 if args.pair else 2]:
+for name, mk in (("small", N.rise_v3_small), ("full", N.rise_v33))[1 if args.split else 0:1 if args.pair else 2]:
     model = mk()
     fl = N.flops_per_position(model)
     if alternate:
         forms = {}
-        first = ("pair", None, "fp16") if args.pair else ("fp8_w4", None, "fp8")
+        first = ("pair", None, "fp16") if args.pair else (f"split{args.split}", None, "fp16") if args.split else ("fp8_w4", None, "fp8")
         for label, waves, w in (first, ("fp16_w4", "4", "fp16"), ("fp16_w8", "8", "fp16")):
             if waves: os.environ["HM_NET_WAVES"] = waves              # read once, by hm_net_create
-            forms[label] = N.FusedNet(model, weights=w, pair=label == "pair")
+            forms[label] = N.FusedNet(model, weights=w, pair=label == "pair", split=args.split if label.startswith("split") else 0)
         os.environ.pop("HM_NET_WAVES", None)
         wbytes = {k: int(f.wh.numel() * 2 + (f.w8.numel() if f.weights == "fp8" else 0)) for k, f in forms.items()}
-        for n in args.rows or (64, 512, 2048):
+        for n in args.rows or ((8, 16, 64, 128) if args.split else (64, 512, 2048)):
             x = torch.rand((n, 74, 8, 8), device="cuda").half()
             for f in forms.values():
                 for _ in range(3): f(x)
@@ -71,3 +74,5 @@ for name, mk in (("small", N.rise_v3_small), ("full", N.rise_v33))[:1 if args.pa
 if alternate:
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     json.dump(out, open(args.out, "w"), indent=1)
+if args.split and forms[f"split{args.split}"].split_error():
+    sys.exit("the team form gave up a launch")
