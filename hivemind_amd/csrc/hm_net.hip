@@ -33,6 +33,7 @@ int hm_fail(int code, const std::string& msg);
 #include "hm_net_w8.hpp"
 #include "hm_net_pair.hpp"      // the pair form (two positions per workgroup): hm_net_set_pair
 #include "hm_net_split.hpp"     // the team form (one position over 2 or 3 workgroups): hm_net_set_split
+#include "hm_net_xboard.hpp"    // the cross-board network (trunk in features form + attention tail): hm_net_create_xboard
 
 namespace hmn {
 
@@ -339,6 +340,8 @@ struct hm_net {
     hmn::PairLaunch pa;
     int split = 0;                           // team form selected (hm_net_set_split): 2 or 3 workgroups per position, every launch goes to rise_forward_split
     hmn::SplitLaunch sa;                     // its workspace is allocated by the first hm_net_set_split and freed by hm_net_destroy
+    bool xb = false;                         // cross-board network (hm_net_create_xboard): every launch goes to xb_launch (two kernels per slice of xa.maxRows rows)
+    hmn::XbLaunch xa;
 };
 
 template <typename K>
@@ -374,8 +377,8 @@ static hipError_t with_narrow(const hm_net* net, F f) {
     if (net->nd.C == 384) return net->k5 ? f(rise_forward_narrow<12, true>) : f(rise_forward_narrow<12, false>);
     return net->k5 ? f(rise_forward_narrow<4, true>) : f(rise_forward_narrow<4, false>);
 }
-int hm_net_can_serve(const hm_net* net) {
-    if (!net || !net->narrow) return 0;
+extern "C" int hm_net_can_serve(const hm_net* net) {
+    if (!net || !net->narrow || net->xb) return 0;
     // narrow_position's policy staging + prior scratch: inside the union region behind Ss, or else in Xs
     const int ldx = net->nd.C + 8, polOff = (65 * std::max(ldx, 88) + 7) & ~7, need = 160 * 64 + hmn::PRIOR_SCRATCH_HALFS;
     return (polOff + need <= net->uHalfs || need <= 65 * ldx) ? 1 : 0;
@@ -532,6 +535,7 @@ int hm_net_create_w8(const int32_t* desc, size_t desc_ints, const void* d_w8, co
 int hm_net_set_pair(hm_net* net, int on) {
     if (!net) return hm_fail(HM_ERR_INVALID, "null argument");
     if (!on) { net->pair = false; return 0; }
+    if (net->xb) return hm_fail(HM_ERR_INVALID, "pair form: cross-board networks are not supported");
     if (net->w8) return hm_fail(HM_ERR_INVALID, "pair form: fp8-weight networks are not supported");
     if (net->split) return hm_fail(HM_ERR_INVALID, "pair form: the handle is in team form (hm_net_set_split)");
     if (!net->narrow) return hm_fail(HM_ERR_INVALID, "pair form: the network does not run the narrow forward");
@@ -556,6 +560,7 @@ int hm_net_set_split(hm_net* net, int t) {
     if (!net) return hm_fail(HM_ERR_INVALID, "null argument");
     if (t == 0) { net->split = 0; return 0; }
     if (t != 2 && t != 3) return hm_fail(HM_ERR_INVALID, "team form: the team size must be 2 or 3");
+    if (net->xb) return hm_fail(HM_ERR_INVALID, "team form: cross-board networks are not supported");
     if (net->w8) return hm_fail(HM_ERR_INVALID, "team form: fp8-weight networks are not supported");
     if (net->pair) return hm_fail(HM_ERR_INVALID, "team form: the handle is in pair form (hm_net_set_pair)");
     if (!net->narrow || net->nd.C != 384) return hm_fail(HM_ERR_INVALID, "team form: the trunk must have 384 channels (narrower trunks leave a member fewer tiles than waves)");
@@ -585,9 +590,44 @@ int hm_net_split_error(const hm_net* net, int* code) {
     if (e != hipSuccess) return hm_fail(HM_ERR_NO_DEVICE, std::string("hm_net_split_error: ") + hipGetErrorString(e));
     return 0;
 }
+// CrossBoardRiseV3 (the reference's crossboard-risev33, src/architectures/rise_mobile_v3.py:242-412; recognised by its loader through
+// the cross_board_blocks. keys, src/main.py:31-33).  desc / d_wh / d_wf as for hm_net_create (the trunk and the value head; the
+// shared policy trunk's entries are unused); tail_desc: hmn::XbDesc as int32s, its offsets into the same two arenas.  The handle owns a
+// feature buffer of max_rows rows; larger batches run in slices of max_rows (trunk, tail, trunk, tail) on the caller's stream.
+int hm_net_create_xboard(const int32_t* desc, size_t desc_ints, const int32_t* tail_desc, size_t tail_ints, const void* d_wh, const void* d_wf, int max_rows, hm_net** out) {
+    if (!tail_desc || !out) return hm_fail(HM_ERR_INVALID, "null argument");
+    if ((reinterpret_cast<uintptr_t>(d_wh) & 15)) return hm_fail(HM_ERR_INVALID, "parameter buffers must be 16-byte aligned");
+    hm_net* net = nullptr;
+    if (int rc = hm_net_create(desc, desc_ints, d_wh, d_wf, &net)) return rc;
+    auto bad = [&](int code, const std::string& m) { hm_net_destroy(net); return hm_fail(code, m); };
+    if (!net->narrow || net->waves != 8) return bad(HM_ERR_INVALID, "cross-board network: the trunk must run the 8-wave narrow forward (64, 128 or 384 channels, input planes padded to 80)");
+    if (net->nd.cv < 1) return bad(HM_ERR_INVALID, "unsupported network geometry");
+    hmn::XbLaunch& a = net->xa;
+    a.d_nd = net->d_nd; a.d_wh = d_wh; a.d_wf = d_wf; a.C = net->nd.C; a.k5 = net->k5; a.copMax = net->copMax; a.uHalfs = net->uHalfs;
+    a.ldsTrunk = net->ldsNarrow; a.maxRows = max_rows;
+    const char* why = "";
+    const hipError_t e = hmn::xb_prepare(a, tail_desc, tail_ints, &why);
+    if (e == hipErrorInvalidValue && *why) return bad(HM_ERR_INVALID, why);
+    if (e != hipSuccess) return bad(HM_ERR_NO_DEVICE, std::string("hm_net_create_xboard: ") + hipGetErrorString(e));
+    net->xb = true;
+    *out = net;
+    return 0;
+}
+// The tail kernel of a cross-board handle alone, on caller-supplied trunk features d_features = fp16 [n][64][C] (16-byte aligned).
+int hm_net_xboard_tail(const hm_net* net, const void* d_features, const void* d_planes, int n,
+                       void* d_value, void* d_pi_a, void* d_pi_b, void* d_wdl, void* d_moves_left, void* stream) {
+    if (!net || !d_features || !d_planes || !d_value || !d_pi_a || !d_pi_b || !d_wdl || !d_moves_left) return hm_fail(HM_ERR_INVALID, "null argument");
+    if (!net->xb) return hm_fail(HM_ERR_INVALID, "hm_net_xboard_tail: not a cross-board network");
+    if (reinterpret_cast<uintptr_t>(d_features) & 15) return hm_fail(HM_ERR_INVALID, "hm_net_xboard_tail: features must be 16-byte aligned");
+    if (n <= 0) return 0;
+    const hipError_t e = hmn::xb_tail(net->xa, net->maxBlocks, static_cast<hipStream_t>(stream), d_features, d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left);
+    if (e != hipSuccess) return hm_fail(HM_ERR_NO_DEVICE, std::string("xboard_tail_kernel: ") + hipGetErrorString(e));
+    return 0;
+}
 int hm_net_destroy(hm_net* net) {
     if (!net) return 0;
     hmn::split_release(net->sa);
+    hmn::xb_release(net->xa);
     if (net->d_nd) (void)hipFree(net->d_nd);
     for (void* p : net->owned) if (p) (void)hipFree(p);
     delete net;
@@ -601,7 +641,10 @@ static int net_forward_impl(const hm_net* net, const void* d_planes, int n, cons
     if (d_group_rows && group <= 0) return hm_fail(HM_ERR_INVALID, "group size must be positive");
     const int grid = n < net->maxBlocks ? n : net->maxBlocks;
     const bool wide = n <= net->wideRows;           // small batches: one workgroup per CU, full register file
-    const hipError_t e = net->w8
+    if (net->xb && d_dbg) return hm_fail(HM_ERR_INVALID, "hm_net_profile: cross-board networks have no phase stamps");
+    const hipError_t e = net->xb
+        ? hmn::xb_launch(net->xa, net->maxBlocks, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_clk)
+        : net->w8
         ? hmn::w8_launch(net->w8a, grid, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_dbg, d_clk)
         : net->split
         ? hmn::split_launch(net->sa, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_clk)

@@ -564,11 +564,13 @@ constexpr int PRIOR_SCRATCH_HALFS = 2 * (HM_MAX_MOVES * 4 + (HM_MAX_MOVES + 8) *
 // PolicyEpi (WT only): called by every thread with the staged logits `pol` ([160][64] fp16 in LDS: board A's 73 planes, then board
 // B's) and `scratch` (the LDS behind them) in place of storing the logits; it ends with a workgroup barrier of its own.
 struct NoPolicyEpi { static constexpr bool present = false; __device__ void operator()(const h16*, unsigned char*) const {} };
-template <int CTILES, bool K5, bool WT = false, typename PolicyEpi = NoPolicyEpi>      // CTILES = C / 32 (2, 4 or 12); cin_pad must be 80
+// FEAT: the features form (the first launch of the cross-board forward, hm_net_xboard.hip): the trunk's output tile is stored to
+// feat as [64][C] fp16 and the position returns before the heads.
+template <int CTILES, bool K5, bool WT = false, typename PolicyEpi = NoPolicyEpi, bool FEAT = false>      // CTILES = C / 32 (2, 4 or 12); cin_pad must be 80
 __device__ __forceinline__ void narrow_position(const NetDesc& nd, const h16* __restrict__ wh, const float* __restrict__ wf, const h16* pin, size_t sIdx,
                                                 int copMax, int uHalfs, unsigned char* smem,
                                                 h16* __restrict__ value, h16* __restrict__ piA, h16* __restrict__ piB, h16* __restrict__ wdl, h16* __restrict__ ml,
-                                                unsigned long long* __restrict__ dbg, int& dbgN, PolicyEpi epi = PolicyEpi()) {
+                                                unsigned long long* __restrict__ dbg, int& dbgN, PolicyEpi epi = PolicyEpi(), h16* __restrict__ feat = nullptr) {
     // C = 64, 128 or 384: an N = C GEMM is CTILES column tiles x 2 square tiles = 2*CTILES tiles of 32x32 over 8 waves, i.e.
     // TPW tiles per wave (tile t = wave + 8i; its square half t & 1 is the wave's own).  copMax = the expanded channels kept
     // in LDS at a time: a block whose `cop` exceeds it (the 384-channel deployed net: cop up to 1152) runs its three phases
@@ -770,6 +772,14 @@ __device__ __forceinline__ void narrow_position(const NetDesc& nd, const h16* __
             }
             __syncthreads();
             HM_STAMP();
+        }
+        if constexpr (FEAT) {
+            for (int i = tid; i < 64 * (C >> 3); i += 512) {
+                const int sq = i / (C >> 3), c8 = i - sq * (C >> 3);
+                *reinterpret_cast<frag4*>(feat + (size_t)sq * C + 8 * c8) = *reinterpret_cast<const frag4*>(Xs + sq * ldx + 8 * c8);
+            }
+            __syncthreads();                                             // Xs is restaged by this workgroup's next position
+            return;
         }
         // ---- value head: 1x1 conv C -> cv (+bias, ReLU), NCHW flatten, linear -> (wdl x3, plys)
         {

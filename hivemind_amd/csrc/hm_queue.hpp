@@ -224,7 +224,7 @@ struct ServeArgs {
 
 struct hm_net;
 // hm_net.hip: 1 when `net` can be the evaluator of the single-launch search (the narrow trunks: C = 64, 128, 384)
-int hm_net_can_serve(const hm_net* net);
+extern "C" int hm_net_can_serve(const hm_net* net);
 // hm_net.hip: 1 when one position takes this network's evaluator much longer than a game needs to collect a batch (the 384-channel trunk)
 int hm_net_serve_is_slow(const hm_net* net);
 // hm_net.hip: what the evaluator role needs of a network handle

@@ -136,6 +136,99 @@ def rise_v3_small() -> RiseV3:
     return RiseV3(128, 128, 32, [3] * 6, [False, False, False, False, True, True], 8, 256)
 
 
+BOARD_CHANNELS = 37          # input planes per board (NB_INPUT_CHANNELS = 2 x 37)
+
+
+class _CrossBoardAttentionBlock(nn.Module):
+    """rise_mobile_v3.py:242-278: both boards are updated from the PREVIOUS tokens of the other board; the memory of a board is the
+    other board's 64 tokens followed by the context tokens; memory_norm serves keys and values alike."""
+
+    def __init__(self, dim, heads, mlp_ratio=2):
+        super().__init__()
+        self.query_norm = nn.LayerNorm(dim)
+        self.memory_norm = nn.LayerNorm(dim)
+        self.cross_attention = nn.MultiheadAttention(dim, heads, dropout=0.0, batch_first=True)
+        self.mlp_norm = nn.LayerNorm(dim)
+        self.mlp = nn.Sequential(nn.Linear(dim, dim * mlp_ratio), nn.GELU(), nn.Linear(dim * mlp_ratio, dim))
+
+    def _update(self, tokens, other, context):
+        memory = self.memory_norm(torch.cat((other, context), dim=1))
+        tokens = tokens + self.cross_attention(self.query_norm(tokens), memory, memory, need_weights=False)[0]
+        return tokens + self.mlp(self.mlp_norm(tokens))
+
+    def forward(self, a, b, context):
+        return self._update(a, b, context), self._update(b, a, context)
+
+
+class _PolicyHead(nn.Module):
+    """_PolicyHead with select_policy_from_plane (builder_util.py:206-239): 3x3, BatchNorm, ReLU, 3x3 to the policy planes."""
+
+    def __init__(self, channels, policy_channels):
+        super().__init__()
+        self.body = nn.Sequential(nn.Conv2d(channels, channels, 3, padding=1, bias=False), nn.BatchNorm2d(channels), nn.ReLU(),
+                                  nn.Conv2d(channels, policy_channels, 3, padding=1, bias=False))
+
+    def forward(self, x):
+        return self.body(x).reshape(x.shape[0], -1)
+
+
+class CrossBoardRiseV3(RiseV3):
+    """CrossBoardRiseV3 (rise_mobile_v3.py:281-412): the RISEv3 trunk, then one token per square and board (1x1 over the trunk
+    features and the board's own 37 planes, + position and board embeddings), seven context tokens (pockets, turns, clock), one or two
+    cross-attention blocks between the boards, a value fusion over both board maps into the usual value head, and one policy head per
+    board on the post-attention maps.  Parameter names mirror the reference; there is no shared policy trunk."""
+
+    def __init__(self, channels=384, channels_operating_init=256, channel_expansion=64, kernels=None, se=None,
+                 channels_value_head=16, value_fc_size=512, attention_dim=192, attention_heads=6, attention_layers=2):
+        super().__init__(channels, channels_operating_init, channel_expansion, kernels, se, channels_value_head, value_fc_size)
+        if attention_layers not in (1, 2):
+            raise ValueError("CrossBoardRiseV3 supports one or two attention layers")
+        d = attention_dim
+        self.board_token_projections = nn.ModuleList([
+            nn.Sequential(nn.Conv2d(channels + BOARD_CHANNELS, d, 1, bias=False), nn.BatchNorm2d(d), nn.ReLU()) for _ in range(2)])
+        self.position_embedding = nn.Parameter(torch.zeros(1, 64, d))
+        self.board_embedding = nn.Parameter(torch.zeros(2, 1, d))
+        self.pocket_projection = nn.Linear(5, d)
+        self.scalar_projection = nn.Linear(1, d)
+        self.context_role_embedding = nn.Parameter(torch.zeros(1, 7, d))
+        self.cross_board_blocks = nn.ModuleList([_CrossBoardAttentionBlock(d, attention_heads) for _ in range(attention_layers)])
+        self.value_fusion = nn.Sequential(nn.Conv2d(2 * d, channels, 1, bias=False), nn.BatchNorm2d(channels), nn.ReLU())
+        self.policy_heads = nn.ModuleList([_PolicyHead(d, POLICY_CHANNELS) for _ in range(2)])
+        for e in (self.position_embedding, self.board_embedding, self.context_role_embedding):
+            nn.init.trunc_normal_(e, std=0.02)
+        self.config.update(attention_dim=d, attention_heads=attention_heads, attention_layers=attention_layers)
+
+    def context_tokens(self, x):
+        o = BOARD_CHANNELS
+        mean = lambda a, b: x[:, a:b].mean(dim=(2, 3))
+        pockets = [self.pocket_projection(v) for v in (mean(12, 17), mean(17, 22), mean(o + 12, o + 17), mean(o + 17, o + 22))]
+        scalars = [self.scalar_projection(v) for v in (mean(25, 26), mean(o + 25, o + 26), mean(31, 32))]
+        return torch.stack((*pockets, *scalars), dim=1) + self.context_role_embedding
+
+    def tail(self, features, x):
+        """Everything after the trunk: features [n, C, 8, 8], x = the input planes."""
+        tokens = [proj(torch.cat((features, planes), dim=1)).flatten(2).transpose(1, 2) + self.position_embedding + self.board_embedding[i]
+                  for i, (proj, planes) in enumerate(zip(self.board_token_projections, x.split(BOARD_CHANNELS, dim=1)))]
+        context = self.context_tokens(x)
+        a, b = tokens
+        for block in self.cross_board_blocks:
+            a, b = block(a, b, context)
+        n = x.shape[0]
+        map_a, map_b = a.transpose(1, 2).reshape(n, -1, 8, 8), b.transpose(1, 2).reshape(n, -1, 8, 8)
+        value, wdl, plys = self.value_head(self.value_fusion(torch.cat((map_a, map_b), dim=1)))
+        return value, self.policy_heads[0](map_a), self.policy_heads[1](map_b), wdl, plys
+
+    def forward(self, x):
+        return self.tail(self.body_spatial(x), x)
+
+
+def cross_board_rise_v33(attention_layers=2) -> CrossBoardRiseV3:
+    """get_cross_board_rise_v33_model (rise_mobile_v3.py:852-888): the rise_v33 trunk with the cross-board tail."""
+    t = rise_v33()
+    blocks = list(t.body_spatial)[1:]
+    return CrossBoardRiseV3(384, 256, 64, t.config["kernels"], [b.se_type is not None for b in blocks], 16, 512, attention_layers=attention_layers)
+
+
 def load_checkpoint(path, model: RiseV3 = None, map_location="cpu") -> RiseV3:
     """Trained-weight ingestion: the reference trainer's checkpoint file, written by save_torch_state
     (src/training/trainer_agent.py:871-890) as torch.save({'model_state_dict', 'optimizer_state_dict',
@@ -154,7 +247,13 @@ def load_checkpoint(path, model: RiseV3 = None, map_location="cpu") -> RiseV3:
         clean[k] = v
     if model is None:
         ch = clean["body_spatial.0.body.0.weight"].shape[0]
-        model = rise_v33() if ch == 384 else rise_v3_small()
+        layers = len({k.split(".")[1] for k in clean if k.startswith("cross_board_blocks.")})       # the reference's loader: src/main.py:31-33
+        if layers:
+            if ch != 384:
+                raise ValueError(f"{path}: a cross-board checkpoint of {ch} channels needs its model passed in")
+            model = cross_board_rise_v33(layers)
+        else:
+            model = rise_v33() if ch == 384 else rise_v3_small()
     model.load_state_dict(clean, strict=True)
     return model.eval()
 
@@ -185,6 +284,8 @@ class InferenceNet(nn.Module):
 
     def __init__(self, model: RiseV3, dtype=torch.float16, device="cuda"):
         super().__init__()
+        if isinstance(model, CrossBoardRiseV3):
+            raise NotImplementedError("InferenceNet holds plain RISEv3 networks; a CrossBoardRiseV3 runs through FusedNet")
         model = model.eval()
         self.dtype = dtype
         mk = lambda w, b, **kw: (w.to(device=device, dtype=dtype).contiguous(memory_format=torch.channels_last),
@@ -329,7 +430,7 @@ class FusedNet:
 
     MAXB, CIN_PAD = 16, 80
 
-    def __init__(self, model: RiseV3, device="cuda", weights="fp16", pair=False, split=0):
+    def __init__(self, model: RiseV3, device="cuda", weights="fp16", pair=False, split=0, max_rows=1024):
         import ctypes as C
         import numpy as np
         from ._lib import lib, check
@@ -343,6 +444,11 @@ class FusedNet:
         self.weights, self.pair, self.split = weights, bool(pair), int(split)
         fp8 = weights == "fp8"
         self._C, self._lib, self._check = C, lib, check
+        if isinstance(model, CrossBoardRiseV3):
+            if fp8 or pair or split:
+                raise ValueError("a CrossBoardRiseV3 runs with fp16 weights, pair=False and split=0")
+            self._init_xboard(copy.deepcopy(model).cpu().float().eval(), device, int(max_rows))
+            return
         model = copy.deepcopy(model).cpu().float().eval()       # packing happens on the host
         halfs, floats, bytes8 = [], [], []
         hoff, foff, boff = [0], [0], [0]
@@ -462,6 +568,129 @@ class FusedNet:
             check(lib.hm_net_set_pair(h, 1))
         if self.split:
             check(lib.hm_net_set_split(h, self.split))
+
+    def _init_xboard(self, model, device, max_rows):
+        """CrossBoardRiseV3 -> hm_net_create_xboard: the trunk descriptor of the plain path (value head included, no shared policy trunk)
+        and the tail's (hmn::XbDesc, hm_net_xboard_device.hpp).  LayerNorm weights and biases are folded into the matrices that follow
+        them (q / k / v, mlp.0), 1/sqrt(head dimension) into q."""
+        import numpy as np
+        C = self._C
+        cfg = model.config
+        if cfg["attention_dim"] != 192 or cfg["attention_heads"] != 6:
+            raise ValueError("the cross-board kernel serves attention_dim=192 with 6 heads")
+        halfs, floats, hoff, foff = [], [], [0], [0]
+
+        def addh(t):
+            t = t.detach().float().reshape(-1)
+            t = torch.cat([t, torch.zeros((-t.numel()) % 8)])
+            halfs.append(t)
+            hoff[0] += t.numel()
+            return hoff[0] - t.numel()
+
+        def addf(t):
+            t = t.detach().float().reshape(-1)
+            floats.append(t)
+            foff[0] += t.numel()
+            return foff[0] - t.numel()
+
+        def conv3_wt(w):                        # [co][ci][3][3] -> Wt[(ky*3+kx)*ci + ci][co], co padded to a multiple of 32
+            co, ci = w.shape[:2]
+            wt = w.permute(2, 3, 1, 0).reshape(9 * ci, co)
+            return torch.cat([wt, torch.zeros(9 * ci, (-co) % 32)], 1)
+
+        lin = lambda w: addh(_pack_frag(w.t().contiguous()))          # Linear weight [out][in] -> packed [K = in][N = out]
+        stem = model.body_spatial[0].body
+        w, b = _fold(stem[0], stem[1])
+        ch = w.shape[0]
+        if ch not in (64, 128, 384):
+            raise ValueError("the cross-board kernel serves trunks of 64, 128 or 384 channels")
+        w = torch.cat([w, torch.zeros(ch, self.CIN_PAD - w.shape[1], 3, 3)], 1)
+        ints = [ch, len(model.body_spatial) - 1, 0, self.CIN_PAD, addh(_pack_frag(w.permute(2, 3, 1, 0).reshape(9 * self.CIN_PAD, ch))), 0, 0]
+        sb = addf(b)
+        blocks = []
+        for blk in list(model.body_spatial)[1:]:
+            body = blk.body
+            w1, b1 = _fold(body[0], body[1])
+            wd, b2 = _fold(body[3], body[4])
+            w2, b3 = _fold(body[6], body[7])
+            cop, k = w1.shape[0], wd.shape[-1]
+            assert cop % 32 == 0 and k in (3, 5)
+            d = [cop, k, 0, 0, addh(_pack_frag(w1.reshape(cop, ch).t().contiguous())), addh(wd.reshape(cop, k * k)),
+                 addh(_pack_frag(w2.reshape(ch, cop).t().contiguous())), 0, addf(b1), addf(b2), addf(b3), 0]
+            if blk.se_type:
+                c1 = blk.se.body[0]
+                d[2], d[7], d[11] = 1, addh(c1.weight.detach()[:, :, c1.kernel_size[0] // 2].t().contiguous()), addf(c1.bias)
+            blocks.append(d)
+        assert len(blocks) <= self.MAXB
+        vh = model.value_head
+        wv, bv = _fold(vh.body[0], vh.body[1])
+        cv = wv.shape[0]
+        assert cv <= 32
+        ints[2] = cv
+        ints += [addh(_pack_frag(torch.cat([wv.reshape(cv, ch).t(), torch.zeros(ch, 32 - cv)], 1).contiguous())),
+                 addh(torch.cat([vh.body_wdl[0].weight, vh.body_plys[0].weight], 0)),
+                 sb, 0, addf(torch.cat([bv, torch.zeros(32 - cv)])), addf(torch.cat([vh.body_wdl[0].bias, vh.body_plys[0].bias]))]
+        for i in range(self.MAXB):
+            ints += blocks[i] if i < len(blocks) else [0] * 12
+        self.desc = np.asarray(ints, dtype=np.int32)
+        # ---- the tail
+        blks = list(model.cross_board_blocks)
+        eps = {float(n.eps) for bl in blks for n in (bl.query_norm, bl.memory_norm, bl.mlp_norm)}
+        assert len(eps) == 1
+        tp_w, tp_b, p1_w, p1_b, p2_w = [], [], [], [], []
+        for i in range(2):
+            proj = model.board_token_projections[i]
+            w, b = _fold(proj[0], proj[1])                          # [192][C + 37][1][1]
+            wt = torch.cat([w.reshape(192, ch + BOARD_CHANNELS).t(), torch.zeros(48 - BOARD_CHANNELS, 192)], 0)      # K = C features + 37 planes, padded to C + 48
+            tp_w.append(addh(_pack_frag(wt.contiguous())))
+            tp_b.append(addf(b))
+            body = model.policy_heads[i].body
+            w, b = _fold(body[0], body[1])
+            p1_w.append(addh(_pack_frag(conv3_wt(w))))
+            p1_b.append(addf(b))
+            p2_w.append(addh(_pack_frag(conv3_wt(body[3].weight.detach().float()))))
+        w, b = _fold(model.value_fusion[0], model.value_fusion[1])
+        tail = [ch, len(blks), int(np.float32(eps.pop()).view(np.int32)), 0, *tp_w, *p1_w, *p2_w, lin(w.reshape(ch, 384)), *tp_b, *p1_b, addf(b),
+                addf(model.position_embedding), addf(model.board_embedding), addf(model.pocket_projection.weight), addf(model.pocket_projection.bias),
+                addf(model.scalar_projection.weight), addf(model.scalar_projection.bias), addf(model.context_role_embedding)]
+        for bl in blks + [None] * (2 - len(blks)):
+            if bl is None:
+                tail += [0] * 12
+                continue
+            att = bl.cross_attention
+            wq, wk, wv_ = att.in_proj_weight.detach().float().split(192)
+            bq, bk, bv_ = att.in_proj_bias.detach().float().split(192)
+            fold = lambda w, b, norm: (w * norm.weight.detach().float()[None, :], w @ norm.bias.detach().float() + b)
+            sc = 1.0 / math.sqrt(192 // 6)
+            wq, bq = fold(wq, bq, bl.query_norm)
+            wk, bk = fold(wk, bk, bl.memory_norm)
+            wv_, bv_ = fold(wv_, bv_, bl.memory_norm)
+            w1, b1 = fold(bl.mlp[0].weight.detach().float(), bl.mlp[0].bias.detach().float(), bl.mlp_norm)
+            tail += [lin(wq * sc), lin(wk), lin(wv_), lin(att.out_proj.weight), lin(w1), lin(bl.mlp[2].weight),
+                     addf(bq * sc), addf(bk), addf(bv_), addf(att.out_proj.bias), addf(b1), addf(bl.mlp[2].bias)]
+        self.tail_desc = np.asarray(tail, dtype=np.int32)
+        self.channels = ch
+        self.wh = torch.cat(halfs).to(device=device, dtype=torch.float16).contiguous()
+        self.wf = torch.cat(floats).to(device=device, dtype=torch.float32).contiguous()
+        self.device = self.wh.device
+        self._out = {}
+        h = C.c_void_p()
+        self._check(self._lib.hm_net_create_xboard(self.desc.ctypes.data, self.desc.size, self.tail_desc.ctypes.data, self.tail_desc.size,
+                                                   self.wh.data_ptr(), self.wf.data_ptr(), max_rows, C.byref(h)))
+        self.handle = h
+        self.weights = "xboard"                  # no plan file (save)
+
+    def tail(self, features: torch.Tensor, planes: torch.Tensor, out=None):
+        """CrossBoardRiseV3 only: the tail kernel alone on trunk features [n, 64, C] fp16 (square-major) and the input planes."""
+        if planes.dtype != torch.float16 or not planes.is_contiguous():
+            planes = planes.to(torch.float16).contiguous()
+        n = planes.shape[0]
+        if features.dtype != torch.float16 or not features.is_contiguous() or tuple(features.shape) != (n, 64, self.channels):
+            raise ValueError("features must be a contiguous fp16 tensor [n, 64, C]")
+        v, a, b, w, m = out if out is not None else self._buffers(n)
+        self._check(self._lib.hm_net_xboard_tail(self.handle, features.data_ptr(), planes.data_ptr(), n, v.data_ptr(), a.data_ptr(), b.data_ptr(),
+                                                 w.data_ptr(), m.data_ptr(), self._C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return v, a, b, w, m
 
     def split_error(self) -> int:
         """Blocking: 0 when no launch of the team form has given up, else the code of the first give-up (cleared by this call)."""

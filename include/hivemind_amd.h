@@ -369,6 +369,24 @@ int hm_net_set_split(hm_net* net, int t);
 /* Blocking (waits for the device): *code = the error word of a handle that is or has been in team form — 0: no launch gave up;
  * 1: a member's partners never arrived; 2: a later wait ran out.  A set word is cleared and the teams' counters are reset. */
 int hm_net_split_error(const hm_net* net, int* code);
+/* CrossBoardRiseV3, the reference's second architecture (crossboard-risev33: src/architectures/rise_mobile_v3.py:242-412, recognised by
+ * its loader through the cross_board_blocks. keys, src/main.py:31-33): the RISEv3 trunk, then one token per square and board, seven
+ * context tokens, one or two cross-attention blocks between the boards, a value fusion and one policy head per board.  desc, d_wh,
+ * d_wf as for hm_net_create (trunk + value head); tail_desc = hmn::XbDesc as int32s (net.py FusedNet), offsets into the same arenas.
+ * Two launches per forward on the caller's stream: the 8-wave trunk in its features form into a buffer of max_rows rows the handle
+ * owns (no allocation inside a forward; larger batches run in slices of max_rows), then the tail kernel.  Trunks of 64 / 128 / 384
+ * channels, 192-dimensional tokens, 6 heads, MLP ratio 2, 73 policy planes; anything else is HM_ERR_INVALID.  The handle serves
+ * hm_net_forward and hm_net_forward_groups[_timed] (the leg clock covers both launches); hm_net_can_serve is 0 for it (the self-play
+ * driver takes its host-driven loop), hm_net_set_pair, hm_net_set_split and hm_net_profile refuse it, it has no plan file and is not
+ * loaded into an hm_engine.  Contract: launches of one such handle must not overlap each other (one stream, or ordered by events):
+ * they share the feature buffer. */
+int hm_net_create_xboard(const int32_t* desc, size_t desc_ints, const int32_t* tail_desc, size_t tail_ints, const void* d_wh, const void* d_wf,
+                         int max_rows, hm_net** out);
+/* The tail kernel of such a handle alone on caller-supplied trunk features d_features = fp16 [n][64][C] (16-byte aligned). */
+int hm_net_xboard_tail(const hm_net* net, const void* d_features, const void* d_planes, int n,
+                       void* d_value, void* d_pi_a, void* d_pi_b, void* d_wdl, void* d_moves_left, void* stream);
+/* 1 when `net` can be the evaluator of the single-launch search (hm_sp_search), else 0 (fp16 trunks of 64 / 128 / 384 channels only). */
+int hm_net_can_serve(const hm_net* net);
 int hm_net_destroy(hm_net* net);
 int hm_net_forward(const hm_net* net, const void* d_planes, int n,
                    void* d_value, void* d_pi_a, void* d_pi_b, void* d_wdl, void* d_moves_left, void* stream);

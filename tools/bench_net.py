@@ -5,7 +5,9 @@ streams (computed from the packed buffers' shapes) to --out.
 --pair: the same alternation for the pair form (two positions per workgroup) of RISEv3-small against the two fp16 forms; the
 384-channel network, which has no pair form, is left out.
 --split T: the same alternation for the team form (T = 2 or 3 workgroups per position) of the deployed 384-channel network against
-the two fp16 forms, at the row counts of one game's search (8, 16, 64, 128 by default); RISEv3-small has no team form."""
+the two fp16 forms, at the row counts of one game's search (8, 16, 64, 128 by default); RISEv3-small has no team form.
+--xboard: cross_board_rise_v33() (trunk in features form + attention tail, two launches) against rise_v33() (8-wave form), alternated
+in the same way at 8, 64 and 512 rows by default; the tail's own time is reported by difference of the two."""
 import argparse, sys, os, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, hivemind_amd as hm
@@ -15,13 +17,14 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--weights", choices=("fp16", "fp8"), default="fp16")
 ap.add_argument("--pair", action="store_true")
 ap.add_argument("--split", type=int, default=0, choices=(0, 2, 3))
+ap.add_argument("--xboard", action="store_true")
 ap.add_argument("--rows", type=int, nargs="+", default=None)
 ap.add_argument("--rounds", type=int, default=4)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 alternate = args.pair or args.split or args.weights == "fp8"
-if args.out is None: args.out = "net_pair.json" if args.pair else "net_split.json" if args.split else "net_fp8.json"
+if args.out is None: args.out = "net_xboard.json" if args.xboard else "net_pair.json" if args.pair else "net_split.json" if args.split else "net_fp8.json"
 hm.init(0)
 torch.manual_seed(0)
 out = {}
@@ -34,6 +37,24 @@ def timed(f, x, iters):
     e.record(); torch.cuda.synchronize()
     return s.elapsed_time(e) / iters
 
+
+if args.xboard:
+    forms = {"xboard": N.FusedNet(N.cross_board_rise_v33()), "rise_v33": N.FusedNet(N.rise_v33())}
+    for n in args.rows or (8, 64, 512):
+        x = torch.rand((n, 74, 8, 8), device="cuda").half()
+        for f in forms.values():
+            for _ in range(3): f(x)
+        torch.cuda.synchronize()
+        ms = {k: [] for k in forms}
+        for _ in range(args.rounds):
+            for k, f in forms.items(): ms[k].append(timed(f, x, args.iters))
+        res = {k: dict(ms=sum(v) / len(v), ms_min=min(v), ms_max=max(v), launches=len(v) * args.iters) for k, v in ms.items()}
+        res["tail_ms_by_difference"] = res["xboard"]["ms"] - res["rise_v33"]["ms"]
+        out[f"rows_{n}"] = res
+        print(n, json.dumps(res), flush=True)
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    json.dump(out, open(args.out, "w"), indent=1)
+    sys.exit(0)
 
 for name, mk in (("small", N.rise_v3_small), ("full", N.rise_v33))[1 if args.split else 0:1 if args.pair else 2]:
     model = mk()
