@@ -72,9 +72,8 @@ __device__ __forceinline__ void search_role(unsigned char* smem, const Pools& pl
         __syncthreads();
     }
     s.g = &s_game;
-    s.ldsCpuct = s_cpuct; s.ldsPwRoot = s_pwRoot; s.ldsPwNode = s_pwNode; s.tabN = TABN;
-    // (every wave: pointers that depend on the wave index compile to flat accesses; only the traversal wave uses them)
-    s.ackSeq = &L.ackSeq; s.typeSeq = &L.typeSeq; s.createSeq = &L.createSeq; s.createFast = &L.createRes.fast; s.gq = &L.gq; s.genAckSeq = &L.gq.ackSeq;
+    s.ldsCpuct = (LdsF32Tab)s_cpuct; s.ldsPwRoot = (LdsU16Tab)s_pwRoot; s.ldsPwNode = (LdsU16Tab)s_pwNode; s.tabN = TABN;
+    s.wl = (LdsWave)&L;                                             // (every wave sets it; only the traversal wave uses it)
     // The game's repetition keys (read by every draw test and hash of the classifier wave, with the search path's keys rebuilt behind
     // them per leaf: path_rebuild_history) in LDS when the game's history and the longest path fit; nothing to write back — the search
     // only appends scratch behind the game's own keys.
@@ -413,8 +412,8 @@ __device__ __forceinline__ void search_role_mg(unsigned char* smem, const Pools&
             for (unsigned i = threadIdx.x; i < sizeof(Game) / 4; i += COLLECT_THREADS) reinterpret_cast<u32*>(&s_game)[i] = reinterpret_cast<const u32*>(gGame)[i];
             __syncthreads();
             s.g = &s_game;
-            s.ldsCpuct = s_cpuct; s.ldsPwRoot = s_pwRoot; s.ldsPwNode = s_pwNode; s.tabN = TABN;
-            if (wave == 0) { s.ackSeq = &L.ackSeq; s.typeSeq = &L.typeSeq; s.createSeq = &L.createSeq; s.createFast = &L.createRes.fast; s.gq = &L.gq; s.genAckSeq = &L.gq.ackSeq; }
+            s.ldsCpuct = (LdsF32Tab)s_cpuct; s.ldsPwRoot = (LdsU16Tab)s_pwRoot; s.ldsPwNode = (LdsU16Tab)s_pwNode; s.tabN = TABN;
+            s.wl = (LdsWave)&L;
             const int rootTeam = s_game.team;
             const bool rootAdv = s_game.adv != 0;
             const int rowBase = g * BATCH;

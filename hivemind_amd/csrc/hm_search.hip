@@ -67,11 +67,10 @@ __global__ __launch_bounds__(COLLECT_THREADS) void k_collect(Pools pl, Params pr
         __syncthreads();
     }
     s.g = &s_game;
-    s.ldsCpuct = s_cpuct; s.ldsPwRoot = s_pwRoot; s.ldsPwNode = s_pwNode; s.tabN = TABN;
+    s.ldsCpuct = (LdsF32Tab)s_cpuct; s.ldsPwRoot = (LdsU16Tab)s_pwRoot; s.ldsPwNode = (LdsU16Tab)s_pwNode; s.tabN = TABN;
     PROF_ADD(9, ta);
     const int wave = threadIdx.x >> 6;
-    s.ackSeq = &L.ackSeq; s.typeSeq = &L.typeSeq; s.createSeq = &L.createSeq; s.createFast = &L.createRes.fast;
-    s.gq = &L.gq; s.genAckSeq = &L.gq.ackSeq;
+    s.wl = (LdsWave)&L;
     if (wave == 0) {
         const int rows = collect_step(s, s_rt, L, planesNext, blockIdx.x);
         if (threadIdx.x == 0) {

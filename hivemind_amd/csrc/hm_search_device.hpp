@@ -230,6 +230,48 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 }
 
 struct GenQ { int node; u32 genOff; int iA, iB; int reqSeq, ackSeq; };   // traversal wave -> generator wave (LDS)
+struct PreSorted { const u32* moves; const float* priors; };   // this game's [2][BATCH][2][HM_MAX_MOVES] arrays sorted by the persistent evaluator
+struct ExpLds {          // per-wave scratch of expand_leaf
+    u32 lists[2][HM_MAX_MOVES];
+    float priors[2][HM_MAX_MOVES + 8];
+};
+struct WaveLds {
+    union {                  // expand_leaf scratch aliases lists[0..4]: never live together (k_raw_policy uses lists[0..1] == exp.lists)
+        u32 lists[NLISTS][HM_MAX_MOVES];
+        ExpLds exp;
+    };
+    u64 board[BATCH][26];    // hm_board images of this batch's network leaves, handed to the plane-writer wave
+    int posted, done;        // hand-off flags (k_collect: wave 0 posts images, wave 1 writes their planes)
+    int postBuf;             // which of the two batches (0/1) the posted leaves belong to
+    int postRow[BATCH];      // plane row of each posted image (ring slot = post number & 7)
+    int postReady[BATCH];    // persistent search: arrivals for each posted image (+1 plane writer, +1 generator, +4 / +8 classifier: network leaf / dropped)
+    int servedCnt;           // posts the plane-writer wave has finished (flow control of the image ring)
+    int servedCntB;          // posts whose board-B move list the generator wave has finished
+    int postCount;           // images posted so far in this launch (classifier wave's counter)
+    int listWords;           // wave 1: move-list words written this launch (traffic accounting)
+    u32 helperLists[2][HM_MAX_MOVES];   // plane-writer wave / generator wave: legal list of the leaf board being served
+    u64 pmask[HM_NB_PLANES + 6];
+    uint32_t pval[HM_NB_PLANES + 6];
+    u64 unavail[8];
+    TrajEnt traj[MAX_TRAJ];
+    // traversal wave -> classifier wave (k_collect): one leaf in flight
+    // (two request slots, used alternately: the traversal may post the next leaf while the classifier is still writing the
+    // previous leaf's context record and board image)
+    TrajEnt trajReq[2][MAX_TRAJ];    // the leaf's path (copied: the traversal reuses `traj` for its next descent)
+    // create != 0: the leaf is a child reached for the first time — the classifier first gives it its position (parent's position +
+    // the joint move), hash and transposition lookup (position_child, canonicalize_child), then classifies it
+    struct Req { int leaf, trajLen, ctxIdx, buf, reserved, first, create, parent, idx; u32 ma, mb; } req[2];
+    int reqSeq, typeSeq, ackSeq, svcStop;   // requests posted / terminal test done / finished; svcStop: no more requests in this launch
+    int createSeq;                   // requests whose creation step is done (resolve_create)
+    struct { int fast, cr, next, reserved; } createRes;   // its outcome: fast = the child is the fresh, reserved leaf the traversal assumed; else canonicalize_child's result (cr 3: pool exhausted)
+    int reqResult;                   // outcome of the last finished request: 0 network leaf, 1 terminal, 2 dropped (not reserved)
+    int svcValid;                    // network leaves of the current batch so far (= plane rows posted)
+    int batchLeaf[BATCH];            // leaves of the batch being collected (same-batch collision test)
+    GenQ gq;
+};
+typedef __attribute__((address_space(3))) WaveLds* LdsWave;   // G carries LDS objects as 32-bit LDS pointers: one scalar register each, ds_ accesses
+typedef const __attribute__((address_space(3))) float* LdsF32Tab;
+typedef const __attribute__((address_space(3))) uint16_t* LdsU16Tab;
 struct G {               // per-wave view of one game's pools
     Game* g;
     Node* nodes;
@@ -245,37 +287,35 @@ struct G {               // per-wave view of one game's pools
     const Params* prm;
     const Pools* pl;
     // first tabN entries of the cpuct / progressive-widening tables staged in LDS by the traversal kernel (0: none)
-    const float* ldsCpuct; const uint16_t* ldsPwRoot; const uint16_t* ldsPwNode; int tabN;
+    LdsF32Tab ldsCpuct; LdsU16Tab ldsPwRoot; LdsU16Tab ldsPwNode; int tabN;
     // k_collect's traversal wave hands every unsolved leaf to the block's classifier wave and goes on selecting; `inflight`
     // is the leaf whose classification has not been acknowledged yet (-1: none).  Its Node must not be read before svc_wait.
     int inflight, reqSeq;
     bool svcBusy;                    // the classifier has not finished the last request (it may still be writing the context / board image)
-    const int* ackSeq;               // requests completely finished
-    const int* typeSeq;              // requests whose terminal test is done (leaf Node final): all the tree guards need
+    // the workgroup's hand-off words of a collect phase (nullptr in kernels without one): WaveLds::ackSeq (requests completely finished),
+    // typeSeq (requests whose terminal test is done: the leaf Node is final — all the tree guards need), createSeq / createRes (below), gq
+    LdsWave wl;
     // same for the generator wave: the node whose candidate generator is being refilled after a pop (its GenHdr and Node::more
     // belong to that wave until gen_wait)
     int genInflight, genReqSeq;
-    const int* genAckSeq;
-    GenQ* gq;
     int nv, es;                      // nodes visited / edges scanned by this launch's descents (flushed to Game once)
     // A child reached for the first time gets its position, hash and transposition lookup from the classifier wave (request with
     // `create` set) while the traversal is already selecting again.  `jPending`: that outcome is still unknown; resolve_create()
     // waits for it at every step the traversal could not take back.
     bool jPending, jTakenBack;
     bool ldsTree;                    // the node pool is the LDS mirror: what the traversal reads of a leaf the classifier wave has finished is LDS only
-    const int* createSeq;            // requests whose creation step is done
-    const int* createFast;           // 1: the child stayed what the traversal assumed (a fresh leaf), 0: the traversal takes the descent back
     u32* dirty;                      // k_collect with the LDS node mirror: one bit per node the launch may have modified (nullptr otherwise)
 };
 // every node that enters a search path (and every first-reached child before canonicalisation) is marked: those, plus the
 // nodes allocated by this launch, are the only ones the launch can have modified, and the only ones written back to HBM
+__device__ __forceinline__ WaveLds& wave_lds(const G& s) { return *(WaveLds*)s.wl; }
 __device__ __forceinline__ void mark_dirty(const G& s, int id) { if (s.dirty) s.dirty[id >> 5] |= 1u << (id & 31); }
 // blocks until the classifier wave has settled the outstanding leaf's terminal test (its writes to the leaf's Node are visible after)
 __device__ __forceinline__ void svc_wait(G& s) {
     if (s.inflight < 0) return;
     PROF_T(tsw);
     HB(11);
-    while (__hip_atomic_load(s.typeSeq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != s.reqSeq) __builtin_amdgcn_s_sleep(1);
+    while (__hip_atomic_load(&wave_lds(s).typeSeq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != s.reqSeq) __builtin_amdgcn_s_sleep(1);
     s.inflight = -1;
     HB(16);
     PROF_ADD(19, tsw);
@@ -286,7 +326,7 @@ __device__ __forceinline__ void svc_join(G& s, int behind = 0) {
     if (!s.svcBusy) return;
     PROF_T(tsw);
     HB(12);
-    while (__hip_atomic_load(s.ackSeq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < s.reqSeq - behind) __builtin_amdgcn_s_sleep(1);
+    while (__hip_atomic_load(&wave_lds(s).ackSeq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < s.reqSeq - behind) __builtin_amdgcn_s_sleep(1);
     if (behind == 0) { s.inflight = -1; s.svcBusy = false; }
     HB(17);
     PROF_ADD(22, tsw);
@@ -295,7 +335,7 @@ __device__ __forceinline__ void gen_wait(G& s) {
     if (s.genInflight < 0) return;
     PROF_T(tgw);
     HB(13);
-    while (__hip_atomic_load(s.genAckSeq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != s.genReqSeq) __builtin_amdgcn_s_sleep(1);
+    while (__hip_atomic_load(&wave_lds(s).gq.ackSeq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != s.genReqSeq) __builtin_amdgcn_s_sleep(1);
     s.genInflight = -1;
     HB(18);
     PROF_ADD(21, tgw);
@@ -306,9 +346,9 @@ __device__ __forceinline__ void gen_wait(G& s) {
 __device__ __forceinline__ bool resolve_create(G& s) {
     if (!s.jPending) return true;
     PROF_T(trc);
-    while (__hip_atomic_load(s.createSeq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != s.reqSeq) __builtin_amdgcn_s_sleep(1);
+    while (__hip_atomic_load(&wave_lds(s).createSeq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != s.reqSeq) __builtin_amdgcn_s_sleep(1);
     s.jPending = false;
-    s.jTakenBack = *s.createFast == 0;
+    s.jTakenBack = wave_lds(s).createRes.fast == 0;
     PROF_ADD(46, trc);
     return !s.jTakenBack;
 }
@@ -881,17 +921,17 @@ __device__ __forceinline__ int descend(G& s, const RulesTab& rt, TrajEnt* traj, 
             GenHdr h = *gh;                                       // header in registers: through the pointer every field access
             HeapEnt he;                                           // is an L2 round trip that later arena stores force to repeat
             PROF_T(tg);
-            const bool async = s.genAckSeq != nullptr;
+            const bool async = s.wl != nullptr;
             const bool got = gen_next(s, h, &he, !async);
             *gh = h;
             if (got && async) {
                 // the successor pushes of the popped pair (visited-set tests, sit-rule closure, frontier growth) run on the
                 // block's generator wave; this node's generator and `more` flag are not read again before gen_wait
                 wave_fence();
-                if ((threadIdx.x & 63) == 0) { s.gq->node = cur; s.gq->genOff = n.gen; s.gq->iA = he.iA; s.gq->iB = he.iB; }
+                if ((threadIdx.x & 63) == 0) { GenQ& q = wave_lds(s).gq; q.node = cur; q.genOff = n.gen; q.iA = he.iA; q.iB = he.iB; }
                 wave_fence();
                 s.genReqSeq++;
-                if ((threadIdx.x & 63) == 0) __hip_atomic_store(&s.gq->reqSeq, s.genReqSeq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if ((threadIdx.x & 63) == 0) __hip_atomic_store(&wave_lds(s).gq.reqSeq, s.genReqSeq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 s.genInflight = cur;
             } else s.nodes[cur].more = h.heapSize > 0;
             PROF_ADD(2, tg);
@@ -1004,46 +1044,6 @@ __device__ inline void write_planes_f16(const RulesTab& rt, const u64* bw /*26 w
     __builtin_amdgcn_wave_barrier();
 }
 
-struct PreSorted { const u32* moves; const float* priors; };   // this game's [2][BATCH][2][HM_MAX_MOVES] arrays sorted by the persistent evaluator
-struct ExpLds {          // per-wave scratch of expand_leaf
-    u32 lists[2][HM_MAX_MOVES];
-    float priors[2][HM_MAX_MOVES + 8];
-};
-struct WaveLds {
-    union {                  // expand_leaf scratch aliases lists[0..4]: never live together (k_raw_policy uses lists[0..1] == exp.lists)
-        u32 lists[NLISTS][HM_MAX_MOVES];
-        ExpLds exp;
-    };
-    u64 board[BATCH][26];    // hm_board images of this batch's network leaves, handed to the plane-writer wave
-    int posted, done;        // hand-off flags (k_collect: wave 0 posts images, wave 1 writes their planes)
-    int postBuf;             // which of the two batches (0/1) the posted leaves belong to
-    int postRow[BATCH];      // plane row of each posted image (ring slot = post number & 7)
-    int postReady[BATCH];    // persistent search: arrivals for each posted image (+1 plane writer, +1 generator, +4 / +8 classifier: network leaf / dropped)
-    int servedCnt;           // posts the plane-writer wave has finished (flow control of the image ring)
-    int servedCntB;          // posts whose board-B move list the generator wave has finished
-    int postCount;           // images posted so far in this launch (classifier wave's counter)
-    int listWords;           // wave 1: move-list words written this launch (traffic accounting)
-    u32 helperLists[2][HM_MAX_MOVES];   // plane-writer wave / generator wave: legal list of the leaf board being served
-    u64 pmask[HM_NB_PLANES + 6];
-    uint32_t pval[HM_NB_PLANES + 6];
-    u64 unavail[8];
-    TrajEnt traj[MAX_TRAJ];
-    // traversal wave -> classifier wave (k_collect): one leaf in flight
-    // (two request slots, used alternately: the traversal may post the next leaf while the classifier is still writing the
-    // previous leaf's context record and board image)
-    TrajEnt trajReq[2][MAX_TRAJ];    // the leaf's path (copied: the traversal reuses `traj` for its next descent)
-    // create != 0: the leaf is a child reached for the first time — the classifier first gives it its position (parent's position +
-    // the joint move), hash and transposition lookup (position_child, canonicalize_child), then classifies it
-    struct Req { int leaf, trajLen, ctxIdx, buf, reserved, first, create, parent, idx; u32 ma, mb; } req[2];
-    int reqSeq, typeSeq, ackSeq, svcStop;   // requests posted / terminal test done / finished; svcStop: no more requests in this launch
-    int createSeq;                   // requests whose creation step is done (resolve_create)
-    struct { int fast, cr, next, reserved; } createRes;   // its outcome: fast = the child is the fresh, reserved leaf the traversal assumed; else canonicalize_child's result (cr 3: pool exhausted)
-    int reqResult;                   // outcome of the last finished request: 0 network leaf, 1 terminal, 2 dropped (not reserved)
-    int svcValid;                    // network leaves of the current batch so far (= plane rows posted)
-    int batchLeaf[BATCH];            // leaves of the batch being collected (same-batch collision test)
-    GenQ gq;
-};
-
 __device__ inline G make_view(const Pools& pl, const Params& prm, int g) {
     G s;
     s.g = pl.games + g;
@@ -1061,9 +1061,9 @@ __device__ inline G make_view(const Pools& pl, const Params& prm, int g) {
     s.leafCounts = pl.leafCounts + (size_t)g * 2 * BATCH * 2;
     s.prm = &prm; s.pl = &pl;
     s.ldsCpuct = nullptr; s.ldsPwRoot = nullptr; s.ldsPwNode = nullptr; s.tabN = 0;
-    s.inflight = -1; s.reqSeq = 0; s.svcBusy = false; s.ackSeq = nullptr; s.typeSeq = nullptr;
-    s.genInflight = -1; s.genReqSeq = 0; s.genAckSeq = nullptr; s.gq = nullptr; s.nv = 0; s.es = 0; s.dirty = nullptr;
-    s.jPending = false; s.jTakenBack = false; s.createSeq = nullptr; s.createFast = nullptr; s.ldsTree = false;
+    s.inflight = -1; s.reqSeq = 0; s.svcBusy = false; s.wl = nullptr;
+    s.genInflight = -1; s.genReqSeq = 0; s.nv = 0; s.es = 0; s.dirty = nullptr;
+    s.jPending = false; s.jTakenBack = false; s.ldsTree = false;
     return s;
 }
 
