@@ -29,6 +29,7 @@
 int hm_fail(int code, const std::string& msg);
 
 #include "hm_net_device.hpp"
+#include "hm_net_plan.hpp"         // narrow_lds_plan, max_cop
 #include "hm_net_w8_device.hpp"    // NetDescW8: the descriptor of a network with FP8 (e4m3) weights
 #include "hm_net_w8.hpp"
 #include "hm_net_pair.hpp"      // the pair form (two positions per workgroup): hm_net_set_pair
@@ -442,21 +443,11 @@ int hm_net_create(const int32_t* desc, size_t desc_ints, const void* d_wh, const
     if (e == hipSuccess && (nd.C == 64 || nd.C == 128 || nd.C == 384) && nd.cin_pad == 80 && !std::getenv("HM_NET_NO_NARROW")) {
         // the 8-wave kernel keeps `copMax` expanded channels of a block in LDS at a time; blocks wider than that (the deployed
         // 384-channel net: up to 1152) are walked in chunks of copMax
-        int copMax = 32;
-        for (int i = 0; i < nd.nblocks; ++i) copMax = std::max(copMax, nd.blk[i].cop);
-        const size_t ldxN = nd.C + 8, ldi = nd.cin_pad + 8;
-        auto bytes_for = [&](int cm) {
-            size_t u = std::max((size_t)cm * 66 + (size_t)64 * (cm + 8), (size_t)65 * std::max(ldxN, ldi));
-            u = (u + 7) & ~(size_t)7;
-            return std::make_pair(u, (65 * ldxN + u) * 2 + (2 * (size_t)cm + nd.C) * 4 + ((((size_t)cm * 25 + 7) & ~(size_t)7) * 2) + (5 * (size_t)nd.C + 64) * 4);
-        };
-        if (const char* ce = std::getenv("HM_NET_COP_CHUNK")) copMax = std::max(64, std::atoi(ce) & ~63);
-        while (copMax > 64 && bytes_for(copMax).second > 160 * 1024) copMax -= 64;      // chunk size: a multiple of 64 channels that fits
-        const auto ub = bytes_for(copMax);
-        if (ub.second <= 160 * 1024) {
-            net->narrow = true; net->copMax = copMax; net->uHalfs = (int)ub.first; net->ldsNarrow = ub.second;
+        const NarrowLdsPlan pl = narrow_lds_plan(nd.C, nd.cin_pad, max_cop(nd, false, "", nullptr), 1, 0);
+        if (pl.ok) {
+            net->narrow = true; net->copMax = pl.copMax; net->uHalfs = pl.uHalfs; net->ldsNarrow = pl.ldsBytes;
             if (const char* we = std::getenv("HM_NET_WAVES")) net->waves = std::atoi(we) == 4 ? 4 : 8;
-            e = with_narrow(net, [&](auto kern) { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ub.second); });
+            e = with_narrow(net, [&](auto kern) { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.ldsBytes); });
         }
     }
     if (e != hipSuccess) { (void)hipFree(net->d_nd); delete net; return hm_fail(HM_ERR_NO_DEVICE, std::string("hm_net_create: ") + hipGetErrorString(e)); }
@@ -494,39 +485,30 @@ int hm_net_create_w8(const int32_t* desc, size_t desc_ints, const void* d_w8, co
     if (nd.nblocks > MAXB || nd.nblocks < 0 || nd.cv > 32 || nd.cv < 1) return bad("unsupported network geometry");
     if ((nd.ps_w | nd.pp_w | nd.v_w) & 1023) return bad("fp8 weights: matrix offsets must be multiples of 1024 bytes");
     bool k5 = false;
-    int copMax = 32;
     for (int i = 0; i < nd.nblocks; ++i) {
         const BlockDescW8& b = nd.blk[i];
         if (b.k != 3 && b.k != 5) return bad("depthwise kernel must be 3 or 5");
-        if (b.cop <= 0 || b.cop % 32) return bad("fp8 weights: expanded channels must be a positive multiple of 32");
         if ((b.w1 | b.w2) & 1023) return bad("fp8 weights: matrix offsets must be multiples of 1024 bytes");
         k5 |= b.k == 5;
-        copMax = std::max(copMax, b.cop);
     }
+    std::string err;
+    const int maxCop = max_cop(nd, true, "fp8 weights", &err);
+    if (maxCop < 0) return bad(err.c_str());
     // LDS plan and chunking rule of the narrow fp16 forms; the chunk's expand scales live in the first 4C floats of the ECA scratch
-    const size_t ldx = nd.C + 8, ldi = nd.cin_pad + 8;
-    auto bytes_for = [&](int cm) {
-        size_t u = std::max((size_t)cm * 66 + (size_t)64 * (cm + 8), (size_t)65 * std::max(ldx, ldi));
-        u = (u + 7) & ~(size_t)7;
-        return std::make_pair(u, (65 * ldx + u) * 2 + (2 * (size_t)cm + nd.C) * 4 + ((((size_t)cm * 25 + 7) & ~(size_t)7) * 2) + (5 * (size_t)nd.C + 64) * 4);
-    };
-    if (const char* ce = std::getenv("HM_NET_COP_CHUNK")) copMax = std::max(64, std::atoi(ce) & ~63);
-    if (copMax > 4 * nd.C) copMax = 4 * nd.C;
-    while (copMax > 64 && bytes_for(copMax).second > 160 * 1024) copMax -= 64;
-    const auto ub = bytes_for(copMax);
-    if (ub.second > 160 * 1024) return bad("network too wide for one LDS tile");
+    const NarrowLdsPlan pl = narrow_lds_plan(nd.C, nd.cin_pad, maxCop, 1, 0, 4 * nd.C);
+    if (!pl.ok) return bad("network too wide for one LDS tile");
     hm_net* net = new hm_net();
     net->w8 = true; net->k5 = k5;
     if (const char* e = std::getenv("HM_NET_MAX_BLOCKS")) net->maxBlocks = std::atoi(e) > 0 ? std::atoi(e) : 1024;
     void* dnd = nullptr;
     if (hipMalloc(&dnd, sizeof(NetDescW8)) != hipSuccess) { delete net; return hm_fail(HM_ERR_NO_DEVICE, "hipMalloc failed"); }
     hipError_t e = hipMemcpy(dnd, &nd, sizeof(NetDescW8), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = w8_set_lds(nd.C, k5, ub.second);
+    if (e == hipSuccess) e = w8_set_lds(nd.C, k5, pl.ldsBytes);
     if (e != hipSuccess) { (void)hipFree(dnd); delete net; return hm_fail(HM_ERR_NO_DEVICE, std::string("hm_net_create_w8: ") + hipGetErrorString(e)); }
     net->owned[0] = dnd;
     W8Launch& a = net->w8a;
     a.d_nd = dnd; a.d_w8 = d_w8; a.d_wh = d_wh; a.d_wf = d_wf;
-    a.C = nd.C; a.k5 = k5; a.copMax = copMax; a.uHalfs = (int)ub.first; a.ldsBytes = ub.second;
+    a.C = nd.C; a.k5 = k5; a.copMax = pl.copMax; a.uHalfs = pl.uHalfs; a.ldsBytes = pl.ldsBytes;
     *out = net;
     return 0;
 }
@@ -542,11 +524,9 @@ int hm_net_set_pair(hm_net* net, int on) {
     if (net->nd.C != 64 && net->nd.C != 128)
         return hm_fail(HM_ERR_INVALID, "pair form: trunk width must be 64 or 128 (two activation and two policy-trunk tiles of a 384-channel trunk exceed one CU's LDS)");
     hmn::PairLaunch a;
-    int maxCop = 32;
-    for (int i = 0; i < net->nd.nblocks; ++i) {
-        if (net->nd.blk[i].cop <= 0 || net->nd.blk[i].cop % 32) return hm_fail(HM_ERR_INVALID, "pair form: expanded channels must be a positive multiple of 32");
-        maxCop = std::max(maxCop, net->nd.blk[i].cop);
-    }
+    std::string err;
+    const int maxCop = hmn::max_cop(net->nd, true, "pair form", &err);
+    if (maxCop < 0) return hm_fail(HM_ERR_INVALID, err);
     if (!hmn::pair_plan(net->nd.C, net->nd.cin_pad, maxCop, a)) return hm_fail(HM_ERR_INVALID, "pair form: two positions do not fit one CU's LDS");
     a.d_nd = net->d_nd; a.d_wh = net->d_wh; a.d_wf = net->d_wf; a.k5 = net->k5;
     const hipError_t e = hmn::pair_set_lds(a);
@@ -565,11 +545,9 @@ int hm_net_set_split(hm_net* net, int t) {
     if (net->pair) return hm_fail(HM_ERR_INVALID, "team form: the handle is in pair form (hm_net_set_pair)");
     if (!net->narrow || net->nd.C != 384) return hm_fail(HM_ERR_INVALID, "team form: the trunk must have 384 channels (narrower trunks leave a member fewer tiles than waves)");
     if (net->split == t) return 0;
-    int maxCop = 32;
-    for (int i = 0; i < net->nd.nblocks; ++i) {
-        if (net->nd.blk[i].cop <= 0 || net->nd.blk[i].cop % 32) return hm_fail(HM_ERR_INVALID, "team form: expanded channels must be a positive multiple of 32");
-        maxCop = std::max(maxCop, net->nd.blk[i].cop);
-    }
+    std::string err;
+    const int maxCop = hmn::max_cop(net->nd, true, "team form", &err);
+    if (maxCop < 0) return hm_fail(HM_ERR_INVALID, err);
     if (net->nd.cv < 1) return hm_fail(HM_ERR_INVALID, "team form: unsupported network geometry");
     net->split = 0;
     hmn::split_release(net->sa);             // another team size: another number of teams

@@ -8,6 +8,7 @@
 
 #include "hm_net_pair_device.hpp"
 #include "hm_net_pair.hpp"
+#include "hm_net_plan.hpp"
 
 namespace hmn {
 
@@ -44,22 +45,10 @@ static hipError_t with_pair(int C, bool k5, F f) {
 }
 
 bool pair_plan(int C, int cinPad, int maxCop, PairLaunch& out) {
-    // the rule of hm_net_create's bytes_for with the per-position parts doubled: both activation tiles, both union regions (input
-    // staging / policy trunk, or the chunk's Y1 + Y2; also the ECA's 32 x C partial sums) and both ECA / head scratches; the chunk's
-    // parameters (b1, b2, b3, depthwise taps) once
-    const size_t ldx = C + 8, ldi = cinPad + 8;
-    auto bytes_for = [&](int cm) {
-        size_t u = std::max({(size_t)cm * 66 + (size_t)64 * (cm + 8), (size_t)65 * std::max(ldx, ldi), (size_t)32 * C * 2});
-        u = (u + 7) & ~(size_t)7;
-        return std::make_pair(u, (2 * 65 * ldx + 2 * u) * 2 + (2 * (size_t)cm + C) * 4 + ((((size_t)cm * 25 + 7) & ~(size_t)7) * 2) + 2 * (5 * (size_t)C + 64) * 4);
-    };
-    int copMax = std::max(32, maxCop);
-    if (const char* ce = std::getenv("HM_NET_COP_CHUNK")) copMax = std::max(64, std::atoi(ce) & ~63);
-    if (copMax > 64 && bytes_for(copMax).second > 160 * 1024) copMax &= ~63;         // chunk size: a multiple of 64 channels that fits
-    while (copMax > 64 && bytes_for(copMax).second > 160 * 1024) copMax -= 64;
-    const auto ub = bytes_for(copMax);
-    if (ub.second > 160 * 1024) return false;
-    out.C = C; out.copMax = copMax; out.uPos = (int)ub.first; out.ldsBytes = ub.second;
+    // narrow_lds_plan with the per-position parts doubled; the union regions state the ECA's 32 x C partial sums as a tenant
+    const NarrowLdsPlan pl = narrow_lds_plan(C, cinPad, maxCop, 2, (size_t)32 * C * 2);
+    if (!pl.ok) return false;
+    out.C = C; out.copMax = pl.copMax; out.uPos = pl.uHalfs; out.ldsBytes = pl.ldsBytes;
     return true;
 }
 
