@@ -56,6 +56,7 @@ _SIGS = {
     "hm_net_create": (_i, [_vp, _sz, _vp, _vp, C.POINTER(_vp)]),
     "hm_net_create_host": (_i, [_vp, _sz, _vp, _sz, _vp, _sz, C.POINTER(_vp)]),
     "hm_net_create_w8": (_i, [_vp, _sz, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "hm_net_create_a8": (_i, [_vp, _sz, _vp, _vp, _vp, C.POINTER(_vp)]),
     "hm_net_set_pair": (_i, [_vp, _i]),
     "hm_net_set_split": (_i, [_vp, _i]),
     "hm_net_split_error": (_i, [_vp, C.POINTER(_i)]),

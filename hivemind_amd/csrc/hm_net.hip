@@ -32,6 +32,8 @@ int hm_fail(int code, const std::string& msg);
 #include "hm_net_plan.hpp"         // narrow_lds_plan, max_cop
 #include "hm_net_w8_device.hpp"    // NetDescW8: the descriptor of a network with FP8 (e4m3) weights
 #include "hm_net_w8.hpp"
+#include "hm_net_a8_device.hpp"    // NetDescA8: the descriptor of a network on native FP8 MFMA (e4m3 activations and weights)
+#include "hm_net_a8.hpp"
 #include "hm_net_pair.hpp"      // the pair form (two positions per workgroup): hm_net_set_pair
 #include "hm_net_split.hpp"     // the team form (one position over 2 or 3 workgroups): hm_net_set_split
 #include "hm_net_xboard.hpp"    // the cross-board network (trunk in features form + attention tail): hm_net_create_xboard
@@ -337,6 +339,8 @@ struct hm_net {
     int wideRows = 256;                      // batches up to this many rows (one workgroup per CU) run the OCC = 1 instantiation
     bool w8 = false;                         // FP8-weight network (hm_net_create_w8): `nd` is unused, every launch goes to rise_forward_w8
     hmn::W8Launch w8a;
+    bool a8 = false;                         // network on native FP8 MFMA (hm_net_create_a8): `nd` is unused, every launch goes to rise_forward_a8
+    hmn::A8Launch a8a;
     bool pair = false;                       // pair form selected (hm_net_set_pair): every launch goes to rise_forward_pair
     hmn::PairLaunch pa;
     int split = 0;                           // team form selected (hm_net_set_split): 2 or 3 workgroups per position, every launch goes to rise_forward_split
@@ -512,13 +516,58 @@ int hm_net_create_w8(const int32_t* desc, size_t desc_ints, const void* d_w8, co
     *out = net;
     return 0;
 }
+// As hm_net_create_w8 with the activations of the quantised GEMMs in e4m3 too, multiplied by the native FP8 MFMA of gfx950
+// (hm_net_a8.hip) — the other half of the reduced-precision plan of nn/engine.cc:290-401, which hm_net_create_w8 covers for the
+// weights only.  desc: hmn::NetDescA8 as a flat int32 array (net.py FusedNet(weights="fp8", acts="fp8")); d_w8: the codes as
+// [K/64][tile][lane][32]; d_wf additionally holds the folded scales sa_in * sw and 1 / sa of the quantised tensors.  Trunks of 128 or
+// 384 channels.  Such a handle runs through hm_net_forward[_groups[_timed]] only; hm_net_can_serve is 0 for it.
+int hm_net_create_a8(const int32_t* desc, size_t desc_ints, const void* d_w8, const void* d_wh, const void* d_wf, hm_net** out) {
+    using namespace hmn;
+    if (!desc || !d_w8 || !d_wh || !d_wf || !out) return hm_fail(HM_ERR_INVALID, "null argument");
+    if (desc_ints * 4 != sizeof(NetDescA8)) return hm_fail(HM_ERR_INVALID, "bad fp8-activation network descriptor size");
+    if ((reinterpret_cast<uintptr_t>(d_w8) & 31) || (reinterpret_cast<uintptr_t>(d_wh) & 15)) return hm_fail(HM_ERR_INVALID, "parameter buffers must be 32-byte (codes) and 16-byte (fp16) aligned");
+    NetDescA8 nd;
+    memcpy(&nd, desc, sizeof(NetDescA8));
+    auto bad = [&](const char* m) { return hm_fail(HM_ERR_INVALID, m); };
+    if (nd.C != 128 && nd.C != 384) return bad("fp8 activations: trunk width must be 128 or 384");
+    if (nd.cin_pad != 80) return bad("fp8 activations: input planes must be padded to 80");
+    if (nd.nblocks > MAXB || nd.nblocks < 0 || nd.cv > 32 || nd.cv < 1) return bad("unsupported network geometry");
+    if ((nd.ps_w | nd.pp_w | nd.v_w) & 2047) return bad("fp8 activations: matrix offsets must be multiples of 2048 bytes");
+    bool k5 = false;
+    for (int i = 0; i < nd.nblocks; ++i) {
+        const BlockDescW8& b = nd.blk[i];
+        if (b.k != 3 && b.k != 5) return bad("depthwise kernel must be 3 or 5");
+        if ((b.w1 | b.w2) & 2047) return bad("fp8 activations: matrix offsets must be multiples of 2048 bytes");
+        if ((b.dw & 7) || (b.ecaw & 7)) return bad("fp8 activations: fp16 offsets must be multiples of 8 halfs");
+        k5 |= b.k == 5;
+    }
+    std::string err;
+    const int maxCop = max_cop(nd, true, "fp8 activations", &err);
+    if (maxCop < 0) return bad(err.c_str());
+    const A8LdsPlan pl = a8_lds_plan(nd.C, nd.cin_pad, maxCop);
+    if (!pl.ok) return bad("network too wide for one LDS tile");
+    hm_net* net = new hm_net();
+    net->a8 = true; net->k5 = k5;
+    if (const char* e = std::getenv("HM_NET_MAX_BLOCKS")) net->maxBlocks = std::atoi(e) > 0 ? std::atoi(e) : 1024;
+    void* dnd = nullptr;
+    if (hipMalloc(&dnd, sizeof(NetDescA8)) != hipSuccess) { delete net; return hm_fail(HM_ERR_NO_DEVICE, "hipMalloc failed"); }
+    hipError_t e = hipMemcpy(dnd, &nd, sizeof(NetDescA8), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = a8_set_lds(nd.C, k5, pl.ldsBytes);
+    if (e != hipSuccess) { (void)hipFree(dnd); delete net; return hm_fail(HM_ERR_NO_DEVICE, std::string("hm_net_create_a8: ") + hipGetErrorString(e)); }
+    net->owned[0] = dnd;
+    A8Launch& a = net->a8a;
+    a.d_nd = dnd; a.d_w8 = d_w8; a.d_wh = d_wh; a.d_wf = d_wf;
+    a.C = nd.C; a.k5 = k5; a.copMax = pl.copMax; a.uBytes = pl.uBytes; a.ldsBytes = pl.ldsBytes;
+    *out = net;
+    return 0;
+}
 // Selects (on != 0) or leaves (on == 0) the pair form for this handle: two positions per 4-wave workgroup, every weight fragment
 // multiplying M = 128 rows (hm_net_pair.hip).  fp16 narrow trunks of 64 or 128 channels; results are bit-identical to the other forms.
 int hm_net_set_pair(hm_net* net, int on) {
     if (!net) return hm_fail(HM_ERR_INVALID, "null argument");
     if (!on) { net->pair = false; return 0; }
     if (net->xb) return hm_fail(HM_ERR_INVALID, "pair form: cross-board networks are not supported");
-    if (net->w8) return hm_fail(HM_ERR_INVALID, "pair form: fp8-weight networks are not supported");
+    if (net->w8 || net->a8) return hm_fail(HM_ERR_INVALID, "pair form: fp8-weight networks are not supported");
     if (net->split) return hm_fail(HM_ERR_INVALID, "pair form: the handle is in team form (hm_net_set_split)");
     if (!net->narrow) return hm_fail(HM_ERR_INVALID, "pair form: the network does not run the narrow forward");
     if (net->nd.C != 64 && net->nd.C != 128)
@@ -541,7 +590,7 @@ int hm_net_set_split(hm_net* net, int t) {
     if (t == 0) { net->split = 0; return 0; }
     if (t != 2 && t != 3) return hm_fail(HM_ERR_INVALID, "team form: the team size must be 2 or 3");
     if (net->xb) return hm_fail(HM_ERR_INVALID, "team form: cross-board networks are not supported");
-    if (net->w8) return hm_fail(HM_ERR_INVALID, "team form: fp8-weight networks are not supported");
+    if (net->w8 || net->a8) return hm_fail(HM_ERR_INVALID, "team form: fp8-weight networks are not supported");
     if (net->pair) return hm_fail(HM_ERR_INVALID, "team form: the handle is in pair form (hm_net_set_pair)");
     if (!net->narrow || net->nd.C != 384) return hm_fail(HM_ERR_INVALID, "team form: the trunk must have 384 channels (narrower trunks leave a member fewer tiles than waves)");
     if (net->split == t) return 0;
@@ -620,8 +669,11 @@ static int net_forward_impl(const hm_net* net, const void* d_planes, int n, cons
     const int grid = n < net->maxBlocks ? n : net->maxBlocks;
     const bool wide = n <= net->wideRows;           // small batches: one workgroup per CU, full register file
     if (net->xb && d_dbg) return hm_fail(HM_ERR_INVALID, "hm_net_profile: cross-board networks have no phase stamps");
+    if (net->a8 && d_dbg) return hm_fail(HM_ERR_INVALID, "hm_net_profile: fp8-activation networks have no phase stamps");
     const hipError_t e = net->xb
         ? hmn::xb_launch(net->xa, net->maxBlocks, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_clk)
+        : net->a8
+        ? hmn::a8_launch(net->a8a, grid, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_clk)
         : net->w8
         ? hmn::w8_launch(net->w8a, grid, static_cast<hipStream_t>(stream), d_planes, n, d_value, d_pi_a, d_pi_b, d_wdl, d_moves_left, d_group_rows, group, d_dbg, d_clk)
         : net->split

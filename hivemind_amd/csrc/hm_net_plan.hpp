@@ -37,6 +37,31 @@ inline NarrowLdsPlan narrow_lds_plan(int C, int cinPad, int maxCop, int position
     return {ub.second <= NARROW_LDS_LIMIT, copMax, (int)ub.first, ub.second};
 }
 
+// The plan of the forward on native FP8 MFMA (the carve-up at the top of narrow_position_a8, hm_net_a8_device.hpp), in bytes:
+//   Xs[64][C+8] fp16 | Xq[65][C+16] codes | union region { input staging [65][cin_pad+8] fp16 , Ss[65][C+16] codes ,
+//   Y1[chunk][66] fp16 + Y2[64][chunk+16] codes , ECA partial sums [32][C] + [4][C] floats } | b1 b2 s1 [chunk] b3[C] |
+//   depthwise taps [chunk][25] | gates [C] + head scratch [64] floats
+// Y2, Ss and the GEMMs' copy of x as bytes pay for Xq: the 384-channel trunk keeps the fp16 forms' chunk of 320 channels.  The chunk is
+// a multiple of 64 (one k-step of the FP8 MFMA).
+struct A8LdsPlan {
+    bool ok;
+    int copMax, uBytes;
+    size_t ldsBytes;
+};
+inline A8LdsPlan a8_lds_plan(int C, int cinPad, int maxCop) {
+    const size_t ldx = C + 8, ldq = C + 16, ldi = cinPad + 8;
+    auto bytes_for = [&](int cm) {
+        size_t u = std::max({(size_t)cm * 132 + (size_t)64 * (cm + 16), 65 * ldq, 65 * ldi * 2, (size_t)36 * C * 4});
+        u = (u + 15) & ~(size_t)15;
+        return std::make_pair(u, 64 * ldx * 2 + 65 * ldq + u + (3 * (size_t)cm + C) * 4 + ((((size_t)cm * 25 + 7) & ~(size_t)7) * 2) + ((size_t)C + 64) * 4);
+    };
+    int copMax = (std::max(64, maxCop) + 63) & ~63;
+    if (const char* ce = std::getenv("HM_NET_COP_CHUNK")) copMax = std::min(copMax, std::max(64, std::atoi(ce) & ~63));   // (measurements, tests)
+    while (copMax > 64 && bytes_for(copMax).second > NARROW_LDS_LIMIT) copMax -= 64;
+    const auto ub = bytes_for(copMax);
+    return {ub.second <= NARROW_LDS_LIMIT, copMax, (int)ub.first, ub.second};
+}
+
 // max(32, the widest `cop` of nd's blocks); requireMultipleOf32: a cop that is no positive multiple of 32 is refused (-1, *err set,
 // prefixed with the form's name)
 template <typename ND>

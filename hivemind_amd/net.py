@@ -417,6 +417,46 @@ def _pack_frag8(codes: torch.Tensor) -> torch.Tensor:
     return x.permute(0, 4, 2, 5, 1, 3).contiguous().reshape(-1)   # p, t, h, c, u, j
 
 
+def _pack_frag8x64(codes: torch.Tensor) -> torch.Tensor:
+    """[K, N] bytes (K % 64 == 0, N % 32 == 0) -> the operand order of v_mfma_scale_f32_32x32x64_f8f6f4 as the kernel reads it,
+    [K/64][tile][lane][32]: lane l holds W[kstep*64 + 32*(l>>5) + j][tile*32 + (l&31)], j = 0..31 (32 bytes per lane, two 16-byte
+    loads; the activation fragment is the same 32 consecutive k values of its LDS row)."""
+    k, n = codes.shape
+    assert k % 64 == 0 and n % 32 == 0, (k, n)
+    x = codes.reshape(k // 64, 2, 32, n // 32, 32)       # ks, h, j, t, c
+    return x.permute(0, 3, 1, 4, 2).contiguous().reshape(-1)      # ks, t, h, c, j
+
+
+def act_scale(amax: float) -> float:
+    """The static scale of one quantised activation tensor: the power of two 2^ceil(log2(2 * amax / 448)) (a factor 2 of headroom
+    over the calibration maximum; a power of two, so that x * (1 / sa) is exact in fp32 and torch and the kernel draw the same codes)."""
+    return 2.0 ** math.ceil(math.log2(2.0 * amax / 448.0)) if amax > 0 else 1.0
+
+
+def quantize_act_e4m3(x: torch.Tensor, sa: float) -> torch.Tensor:
+    """The activation quantisation step of acts="fp8": clamp(x / sa, -448, 448), round-to-nearest-even to OCP e4m3 (uint8 codes)."""
+    return (x.float() / sa).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+@torch.no_grad()
+def calibrate_act_scales(model: "RiseV3", planes: torch.Tensor):
+    """The 2 * nblocks + 2 activation scales of FusedNet(acts="fp8"), from the maxima of the (BatchNorm-folded = eval-mode) model in
+    fp32 on the calibration planes, on the planes' device: per block its input after the ECA gate and its depthwise output, then the
+    trunk output and the policy trunk's output."""
+    import copy
+    m = copy.deepcopy(model).float().eval().to(planes.device)
+    x = m.body_spatial[0](planes.float())
+    amax = []
+    for blk in list(m.body_spatial)[1:]:
+        if blk.se_type:
+            x = blk.se(x)
+        y = blk.body[:6](x)                                       # expand, depthwise (each + BatchNorm, ReLU)
+        amax += [x.abs().max(), y.abs().max()]
+        x = x + blk.body[6:](y)
+    amax += [x.abs().max(), m.policy_heads.shared_body(x).abs().max()]
+    return [act_scale(float(a)) for a in amax]
+
+
 class FusedNet:
     """RiseV3 (eval) -> one hm_net_forward launch per batch.  Same output contract as InferenceNet.
     weights="fp8": the 1x1 expand / project, policy-trunk, policy-projection and value convolutions are stored and fetched as
@@ -426,11 +466,14 @@ class FusedNet:
     M = 128 rows; fp16 trunks of 64 / 128 channels).  Same results bit for bit; the plan file does not record the form.
     split=2 or 3: the team form (hm_net_set_split: every position of the fp16 384-channel trunk is carried by that many workgroups
     inside the one launch, each streaming its share of the weights).  Same results bit for bit; launches of team-form networks must
-    not overlap each other (one stream); split_error() tells whether a launch gave up."""
+    not overlap each other (one stream); split_error() tells whether a launch gave up.
+    acts="fp8" (with weights="fp8"; trunks of 128 / 384 channels): the same five GEMM families on the native FP8 MFMA, their
+    activations quantised to e4m3 too with one static power-of-two scale per tensor (hm_net_create_a8) — calibrated on
+    calibration=planes by calibrate_act_scales, or given as act_scales=[2 * nblocks + 2 powers of two].  Not the default."""
 
     MAXB, CIN_PAD = 16, 80
 
-    def __init__(self, model: RiseV3, device="cuda", weights="fp16", pair=False, split=0, max_rows=1024):
+    def __init__(self, model: RiseV3, device="cuda", weights="fp16", pair=False, split=0, max_rows=1024, acts="fp16", calibration=None, act_scales=None):
         import ctypes as C
         import numpy as np
         from ._lib import lib, check
@@ -441,7 +484,25 @@ class FusedNet:
             raise ValueError("pair=True needs fp16 weights")
         if split and (pair or weights == "fp8"):
             raise ValueError("split needs fp16 weights and pair=False")
-        self.weights, self.pair, self.split = weights, bool(pair), int(split)
+        if acts not in ("fp16", "fp8"):
+            raise ValueError("acts must be 'fp16' or 'fp8'")
+        a8 = acts == "fp8"
+        if a8:
+            if weights != "fp8":
+                raise ValueError("acts='fp8' needs weights='fp8'")
+            if pair or split:
+                raise ValueError("acts='fp8' has no pair or team form")
+            if isinstance(model, CrossBoardRiseV3):
+                raise ValueError("a CrossBoardRiseV3 runs with fp16 weights and activations")
+            if model.body_spatial[0].body[0].out_channels not in (128, 384):
+                raise ValueError("acts='fp8' serves trunks of 128 or 384 channels")
+            if act_scales is None and calibration is None:
+                raise ValueError("acts='fp8' needs calibration planes or act_scales")
+            sa = [float(v) for v in act_scales] if act_scales is not None else calibrate_act_scales(model, calibration)
+            if len(sa) != 2 * (len(model.body_spatial) - 1) + 2 or any(not (v > 0 and math.isfinite(v) and math.frexp(v)[0] == 0.5) for v in sa):
+                raise ValueError("act_scales must be 2 * nblocks + 2 positive powers of two")
+            self.act_scales = sa
+        self.weights, self.pair, self.split, self.acts = weights, bool(pair), int(split), acts
         fp8 = weights == "fp8"
         self._C, self._lib, self._check = C, lib, check
         if isinstance(model, CrossBoardRiseV3):
@@ -453,10 +514,13 @@ class FusedNet:
         halfs, floats, bytes8 = [], [], []
         hoff, foff, boff = [0], [0], [0]
 
-        def addq(wt):          # fp8: [K, N] -> (byte offset of the packed codes, float offset of the scales)
+        def addq(wt, si=0):    # fp8: [K, N] -> (byte offset of the packed codes, float offset of the scales)
             codes, scale = quantize_e4m3(wt)
+            if a8:             # K padded to the MFMA's 64 with zero rows; the input tensor's scale sa[si] folded into the weight scales
+                codes = torch.cat([codes, torch.zeros((-codes.shape[0]) % 64, codes.shape[1], dtype=torch.uint8)])
+                scale = scale * sa[si]
             off = boff[0]
-            bytes8.append(_pack_frag8(codes))
+            bytes8.append(_pack_frag8x64(codes) if a8 else _pack_frag8(codes))
             boff[0] += codes.numel()
             return off, addf(scale)
 
@@ -495,7 +559,8 @@ class FusedNet:
         desc["stem_w"] = addh(_pack_frag(conv3_wt(w, self.CIN_PAD)))
         desc["stem_b"] = addf(b)
         blocks = []
-        for blk in list(model.body_spatial)[1:]:
+        nb = len(model.body_spatial) - 1
+        for bi, blk in enumerate(list(model.body_spatial)[1:]):
             body = blk.body
             w1, b1 = _fold(body[0], body[1])
             wd, b2 = _fold(body[3], body[4])
@@ -504,14 +569,14 @@ class FusedNet:
             assert cop % 32 == 0 and k in (3, 5)
             d = dict(cop=cop, k=k, eca=0, ecaw=0, ecab=0)
             if fp8:
-                d["w1"], d["s1"] = addq(w1.reshape(cop, ch).t().contiguous())
+                d["w1"], d["s1"] = addq(w1.reshape(cop, ch).t().contiguous(), 2 * bi)
             else:
                 d["w1"] = addh(_pack_frag(w1.reshape(cop, ch).t().contiguous()))
             d["b1"] = addf(b1)
             d["dw"] = addh(wd.reshape(cop, k * k))
             d["b2"] = addf(b2)
             if fp8:
-                d["w2"], d["s3"] = addq(w2.reshape(ch, cop).t().contiguous())
+                d["w2"], d["s3"] = addq(w2.reshape(ch, cop).t().contiguous(), 2 * bi + 1)
             else:
                 d["w2"] = addh(_pack_frag(w2.reshape(ch, cop).t().contiguous()))
             d["b3"] = addf(b3)
@@ -529,7 +594,7 @@ class FusedNet:
         assert cv <= 32
         desc["cv"] = cv
         if fp8:
-            desc["v_w"], desc["v_s"] = addq(padn(wv.reshape(cv, ch).t().contiguous(), 32))
+            desc["v_w"], desc["v_s"] = addq(padn(wv.reshape(cv, ch).t().contiguous(), 32), 2 * nb)
         else:
             desc["v_w"] = addh(_pack_frag(padn(wv.reshape(cv, ch).t().contiguous(), 32)))
         desc["v_b"] = addf(torch.cat([bv, torch.zeros(32 - cv)]))
@@ -538,13 +603,15 @@ class FusedNet:
         ph = model.policy_heads
         ws, bs = _fold(ph.shared_body[0], ph.shared_body[1])
         if fp8:
-            desc["ps_w"], desc["ps_s"] = addq(conv3_wt(ws))
+            desc["ps_w"], desc["ps_s"] = addq(conv3_wt(ws), 2 * nb)
         else:
             desc["ps_w"] = addh(_pack_frag(conv3_wt(ws)))
         desc["ps_b"] = addf(bs)
         wp = torch.cat([ph.board_projections[0].weight.detach().float(), ph.board_projections[1].weight.detach().float()], 0)
         if fp8:
-            desc["pp_w"], desc["pp_s"] = addq(padn(conv3_wt(wp), 160))
+            desc["pp_w"], desc["pp_s"] = addq(padn(conv3_wt(wp), 160), 2 * nb + 1)
+            if a8:
+                desc["qinv"] = addf(1.0 / torch.tensor(sa, dtype=torch.float64))
             self._init_w8(desc, blocks, halfs, floats, bytes8, device)
             return
         desc["pp_w"] = addh(_pack_frag(padn(conv3_wt(wp), 160)))
@@ -699,11 +766,15 @@ class FusedNet:
         return code.value
 
     def _init_w8(self, desc, blocks, halfs, floats, bytes8, device):
-        """The fp8 network's descriptor (hmn::NetDescW8, hm_net_w8_device.hpp) and its three parameter buffers."""
+        """The fp8 network's descriptor (hmn::NetDescW8, hm_net_w8_device.hpp; acts="fp8": hmn::NetDescA8, hm_net_a8_device.hpp, the
+        same with the offset of the 1 / sa table behind the header) and its three parameter buffers."""
         import numpy as np
         C = self._C
         ints = [desc["C"], len(blocks), desc["cv"], desc["cin_pad"], desc["stem_w"], desc["vl_w"], desc["ps_w"], desc["pp_w"], desc["v_w"],
                 desc["stem_b"], desc["ps_b"], desc["v_b"], desc["vl_b"], desc["ps_s"], desc["pp_s"], desc["v_s"]]
+        a8 = self.acts == "fp8"
+        if a8:
+            ints += [desc["qinv"], 0]
         for i in range(self.MAXB):
             if i < len(blocks):
                 d = blocks[i]
@@ -717,7 +788,8 @@ class FusedNet:
         self.device = self.wh.device
         self._out = {}
         h = C.c_void_p()
-        self._check(self._lib.hm_net_create_w8(self.desc.ctypes.data, self.desc.size, self.w8.data_ptr(), self.wh.data_ptr(), self.wf.data_ptr(), C.byref(h)))
+        create = self._lib.hm_net_create_a8 if a8 else self._lib.hm_net_create_w8
+        self._check(create(self.desc.ctypes.data, self.desc.size, self.w8.data_ptr(), self.wh.data_ptr(), self.wf.data_ptr(), C.byref(h)))
         self.handle = h
 
     def close(self):

@@ -348,6 +348,15 @@ int hm_net_create_host(const int32_t* desc, size_t desc_ints, const void* h_wh, 
  * hm_net_forward, hm_net_forward_groups[_timed], hm_net_profile and hm_net_destroy; it cannot be the evaluator of
  * hm_sp_search (the self-play driver then takes its host-driven loop). */
 int hm_net_create_w8(const int32_t* desc, size_t desc_ints, const void* d_w8, const void* d_wh, const void* d_wf, hm_net** out);
+/* The same network with the activations of those GEMMs in e4m3 too, multiplied by the native FP8 MFMA of gfx950
+ * (v_mfma_scale_f32_32x32x64_f8f6f4): the activation half of the reduced-precision plan of nn/engine.cc:290-401, of which
+ * hm_net_create_w8 is the weight half (it decodes the codes to fp16 in front of the fp16 MFMA; this form replaces that decode).
+ * One static power-of-two scale per quantised tensor (2 * nblocks + 2 of them, calibrated by net.py calibrate_act_scales);
+ * desc = hmn::NetDescA8 as int32s (net.py FusedNet(weights="fp8", acts="fp8")), d_w8 = the codes as [K/64][tile][lane][32]
+ * (32-byte aligned), d_wf additionally the folded scales and 1 / sa.  Trunks of 128 / 384 channels, input planes padded to 80.
+ * The handle serves hm_net_forward, hm_net_forward_groups[_timed] and hm_net_destroy; hm_net_can_serve is 0 for it,
+ * hm_net_set_pair, hm_net_set_split and hm_net_profile refuse it, and it has no plan file. */
+int hm_net_create_a8(const int32_t* desc, size_t desc_ints, const void* d_w8, const void* d_wh, const void* d_wf, hm_net** out);
 /* The pair form of the forward for this handle: on != 0 makes hm_net_forward, hm_net_forward_groups[_timed] and hm_net_profile
  * run two positions (rows 2p, 2p + 1) per 4-wave workgroup, every weight fragment multiplying M = 128 rows; on == 0 restores the
  * previous form.  Results are bit-identical to the other forms, rows outside a group's count stay untouched.  fp16 trunks of 64 or

@@ -2,6 +2,8 @@
 --weights fp8: the fp8-weight form against the two fp16 forms (4-wave: HM_NET_WAVES=4, 8-wave default) in one process, the forms
 alternated round by round, device events over >= 20 launches each; writes ms per launch, TFLOP/s and the weight bytes a position
 streams (computed from the packed buffers' shapes) to --out.
+--acts fp8: the same alternation for the form on native FP8 MFMA (e4m3 activations and weights, 8 waves; scales calibrated on random
+planes) against the fp8-weight form (4 waves) and the fp16 8-wave default.
 --pair: the same alternation for the pair form (two positions per workgroup) of RISEv3-small against the two fp16 forms; the
 384-channel network, which has no pair form, is left out.
 --split T: the same alternation for the team form (T = 2 or 3 workgroups per position) of the deployed 384-channel network against
@@ -15,6 +17,7 @@ from hivemind_amd import net as N
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--weights", choices=("fp16", "fp8"), default="fp16")
+ap.add_argument("--acts", choices=("fp16", "fp8"), default="fp16")
 ap.add_argument("--pair", action="store_true")
 ap.add_argument("--split", type=int, default=0, choices=(0, 2, 3))
 ap.add_argument("--xboard", action="store_true")
@@ -23,8 +26,8 @@ ap.add_argument("--rounds", type=int, default=4)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
-alternate = args.pair or args.split or args.weights == "fp8"
-if args.out is None: args.out = "net_xboard.json" if args.xboard else "net_pair.json" if args.pair else "net_split.json" if args.split else "net_fp8.json"
+alternate = args.pair or args.split or args.weights == "fp8" or args.acts == "fp8"
+if args.out is None: args.out = "net_xboard.json" if args.xboard else "net_pair.json" if args.pair else "net_split.json" if args.split else "net_a8.json" if args.acts == "fp8" else "net_fp8.json"
 hm.init(0)
 torch.manual_seed(0)
 out = {}
@@ -62,9 +65,13 @@ for name, mk in (("small", N.rise_v3_small), ("full", N.rise_v33))[1 if args.spl
     if alternate:
         forms = {}
         first = ("pair", None, "fp16") if args.pair else (f"split{args.split}", None, "fp16") if args.split else ("fp8_w4", None, "fp8")
-        for label, waves, w in (first, ("fp16_w4", "4", "fp16"), ("fp16_w8", "8", "fp16")):
+        others = (("fp8_w4", None, "fp8"), ("fp16_w8", "8", "fp16")) if args.acts == "fp8" else (("fp16_w4", "4", "fp16"), ("fp16_w8", "8", "fp16"))
+        if args.acts == "fp8":
+            first = ("a8_w8", None, "fp8")
+            calib = dict(acts="fp8", calibration=torch.rand((64, 74, 8, 8), device="cuda"))
+        for label, waves, w in (first, *others):
             if waves: os.environ["HM_NET_WAVES"] = waves              # read once, by hm_net_create
-            forms[label] = N.FusedNet(model, weights=w, pair=label == "pair", split=args.split if label.startswith("split") else 0)
+            forms[label] = N.FusedNet(model, weights=w, pair=label == "pair", split=args.split if label.startswith("split") else 0, **(calib if label == "a8_w8" else {}))
         os.environ.pop("HM_NET_WAVES", None)
         wbytes = {k: int(f.wh.numel() * 2 + (f.w8.numel() if f.weights == "fp8" else 0)) for k, f in forms.items()}
         for n in args.rows or ((8, 16, 64, 128) if args.split else (64, 512, 2048)):
