@@ -59,6 +59,7 @@ _SIGS = {
     "hm_net_create_a8": (_i, [_vp, _sz, _vp, _vp, _vp, C.POINTER(_vp)]),
     "hm_net_set_pair": (_i, [_vp, _i]),
     "hm_net_set_split": (_i, [_vp, _i]),
+    "hm_net_set_serve": (_i, [_vp, _i]),
     "hm_net_split_error": (_i, [_vp, C.POINTER(_i)]),
     "hm_net_create_xboard": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _i, C.POINTER(_vp)]),
     "hm_net_xboard_tail": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

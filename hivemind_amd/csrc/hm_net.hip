@@ -341,6 +341,8 @@ struct hm_net {
     hmn::W8Launch w8a;
     bool a8 = false;                         // network on native FP8 MFMA (hm_net_create_a8): `nd` is unused, every launch goes to rise_forward_a8
     hmn::A8Launch a8a;
+    bool serve = false;                      // a8 only: serve form selected (hm_net_set_serve): the handle can be the evaluator of the single-launch search
+    hmn::A8ServePlan a8s{};                  // its LDS plan (the stand-alone forward keeps a8a's)
     bool pair = false;                       // pair form selected (hm_net_set_pair): every launch goes to rise_forward_pair
     hmn::PairLaunch pa;
     int split = 0;                           // team form selected (hm_net_set_split): 2 or 3 workgroups per position, every launch goes to rise_forward_split
@@ -383,14 +385,23 @@ static hipError_t with_narrow(const hm_net* net, F f) {
     return net->k5 ? f(rise_forward_narrow<4, true>) : f(rise_forward_narrow<4, false>);
 }
 extern "C" int hm_net_can_serve(const hm_net* net) {
+    if (net && net->a8) return net->serve ? 1 : 0;
     if (!net || !net->narrow || net->xb) return 0;
     // narrow_position's policy staging + prior scratch: inside the union region behind Ss, or else in Xs
     const int ldx = net->nd.C + 8, polOff = (65 * std::max(ldx, 88) + 7) & ~7, need = 160 * 64 + hmn::PRIOR_SCRATCH_HALFS;
     return (polOff + need <= net->uHalfs || need <= 65 * ldx) ? 1 : 0;
 }
-int hm_net_serve_is_slow(const hm_net* net) { return net && net->nd.C >= 384 ? 1 : 0; }
+int hm_net_serve_is_slow(const hm_net* net) { return net && (net->a8 ? net->a8a.C : net->nd.C) >= 384 ? 1 : 0; }
 int hm_net_serve_info_get(const hm_net* net, hm_net_serve_info* out) {
     if (!hm_net_can_serve(net) || !out) return hm_fail(HM_ERR_INVALID, "this network cannot be the evaluator of the single-launch search");
+    *out = hm_net_serve_info{};
+    if (net->a8) {
+        const hmn::A8Launch& a = net->a8a;
+        out->d_nd = a.d_nd; out->d_wh = a.d_wh; out->d_wf = a.d_wf; out->d_w8 = a.d_w8;
+        out->C = a.C; out->k5 = a.k5 ? 1 : 0; out->copMax = net->a8s.copMax; out->uBytes = net->a8s.uBytes; out->polOff = net->a8s.polOff;
+        out->ldsBytes = net->a8s.ldsBytes; out->form = HM_SERVE_A8;
+        return 0;
+    }
     out->d_nd = net->d_nd; out->d_wh = net->d_wh; out->d_wf = net->d_wf;
     out->C = net->nd.C; out->k5 = net->k5 ? 1 : 0; out->copMax = net->copMax; out->uHalfs = net->uHalfs; out->ldsBytes = net->ldsNarrow;
     return 0;
@@ -520,7 +531,7 @@ int hm_net_create_w8(const int32_t* desc, size_t desc_ints, const void* d_w8, co
 // (hm_net_a8.hip) — the other half of the reduced-precision plan of nn/engine.cc:290-401, which hm_net_create_w8 covers for the
 // weights only.  desc: hmn::NetDescA8 as a flat int32 array (net.py FusedNet(weights="fp8", acts="fp8")); d_w8: the codes as
 // [K/64][tile][lane][32]; d_wf additionally holds the folded scales sa_in * sw and 1 / sa of the quantised tensors.  Trunks of 128 or
-// 384 channels.  Such a handle runs through hm_net_forward[_groups[_timed]] only; hm_net_can_serve is 0 for it.
+// 384 channels.  Such a handle runs through hm_net_forward[_groups[_timed]]; hm_net_can_serve is 0 for it until hm_net_set_serve.
 int hm_net_create_a8(const int32_t* desc, size_t desc_ints, const void* d_w8, const void* d_wh, const void* d_wf, hm_net** out) {
     using namespace hmn;
     if (!desc || !d_w8 || !d_wh || !d_wf || !out) return hm_fail(HM_ERR_INVALID, "null argument");
@@ -557,8 +568,24 @@ int hm_net_create_a8(const int32_t* desc, size_t desc_ints, const void* d_w8, co
     net->owned[0] = dnd;
     A8Launch& a = net->a8a;
     a.d_nd = dnd; a.d_w8 = d_w8; a.d_wh = d_wh; a.d_wf = d_wf;
-    a.C = nd.C; a.k5 = k5; a.copMax = pl.copMax; a.uBytes = pl.uBytes; a.ldsBytes = pl.ldsBytes;
+    a.C = nd.C; a.k5 = k5; a.copMax = pl.copMax; a.uBytes = pl.uBytes; a.ldsBytes = pl.ldsBytes; a.cinPad = nd.cin_pad; a.maxCop = maxCop;
     *out = net;
+    return 0;
+}
+// Selects (on != 0) or leaves (on == 0) the serve form of a network on native FP8 MFMA (hm_net_create_a8): the handle can then be the
+// evaluator of the single-launch search (hm_net_can_serve is 1; hm_sp_search launches k_rollout_a8, hm_rollout.hip) — the role
+// Engine::enqueueInferenceHalf / synchronizeInferenceHalf (nn/engine.h:43-81) play for the reference's search threads, here with the
+// reduced-precision engine of nn/engine.cc:290-401.  Its LDS plan (a8_serve_plan) keeps the leaf's policy logits and the prior
+// pipeline's scratch behind the policy trunk's tile; a network whose layout then exceeds one CU's LDS is refused.  The stand-alone
+// forward of the handle is unaffected.  Any other handle: HM_ERR_INVALID.
+int hm_net_set_serve(hm_net* net, int on) {
+    if (!net) return hm_fail(HM_ERR_INVALID, "null argument");
+    if (!net->a8) return hm_fail(HM_ERR_INVALID, "serve form: only networks on native FP8 MFMA (hm_net_create_a8) have one");
+    if (!on) { net->serve = false; return 0; }
+    const hmn::A8Launch& a = net->a8a;
+    const hmn::A8ServePlan pl = hmn::a8_serve_plan(a.C, a.cinPad, a.maxCop, 160 * 64 * 2 + hmn::PRIOR_SCRATCH_BYTES);
+    if (!pl.ok) return hm_fail(HM_ERR_INVALID, "serve form: the policy staging does not fit one CU's LDS beside the network's tiles");
+    net->a8s = pl; net->serve = true;        // (the dynamic-LDS attribute of k_rollout_a8 is raised by hm_sp_search, which knows the search role's share)
     return 0;
 }
 // Selects (on != 0) or leaves (on == 0) the pair form for this handle: two positions per 4-wave workgroup, every weight fragment

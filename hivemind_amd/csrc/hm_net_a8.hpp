@@ -14,6 +14,7 @@ struct A8Launch {
     const void* d_wh = nullptr;     // fp16 parameters (stem, depthwise, ECA, value linear)
     const void* d_wf = nullptr;     // fp32 biases, folded scales, 1 / activation scales
     int C = 0, copMax = 0, uBytes = 0;
+    int cinPad = 0, maxCop = 0;     // what a8_lds_plan was given (hm_net_set_serve plans the serve form from the same)
     bool k5 = false;
     size_t ldsBytes = 0;
 };

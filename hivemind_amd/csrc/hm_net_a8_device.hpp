@@ -28,7 +28,8 @@
 // consecutive rows by four banks, as the fp16 tiles' does) | union{ input staging [65][88] fp16, Ss[65][C+16] codes,
 // Y1[copMax][66] fp16 + Y2[64][chunk64+16] codes, ECA partial sums } | b1 b2 s1 [copMax] b3[C] | depthwise taps | gates + head scratch.
 // A chunk of the expansion is a multiple of 64 channels except the last of a block, whose 32 missing channels are zero codes in Y2
-// against zero weight rows.
+// against zero weight rows.  The serve form (WT) adds one tenant to the union region: Pol[160][64] fp16 + PolicyEpi's scratch behind Sq
+// (a8_serve_plan).
 #pragma once
 #include "hm_net_w8_device.hpp"   // BlockDescW8, and hm_net_device.hpp: the stem's fp16 GEMM, drow, im2col_row, frag4
 
@@ -202,10 +203,16 @@ __device__ __forceinline__ void depthwise_rows_q8(const h16* y1, uint8_t* y2, in
 
 // One position through the whole network by one workgroup of eight waves.  CTILES = C / 32 (4 or 12); cin_pad must be 80; copMax (a
 // multiple of 64) and uBytes come from a8_lds_plan.
-template <int CTILES, bool K5>
+// WT (the serve form: the evaluator role of the single-launch search, hm_rollout.hip): the value head leaves through write-through
+// stores (hm_queue.hpp) and the policy logits go to the LDS staging tile Pol[160][64] fp16 at byte `polOff` of the union region, behind
+// Sq — then PolicyEpi (hm_net_device.hpp) works on them in place with the LDS behind Pol as its scratch, or, without one, they are
+// stored as 16-byte write-through chunks.  polOff and the uBytes that hold the staging come from a8_serve_plan; a logit is rounded to
+// fp16 once, from the fp32 value the stand-alone form stores.
+template <int CTILES, bool K5, bool WT = false, typename PolicyEpi = NoPolicyEpi>
 __device__ __forceinline__ void narrow_position_a8(const NetDescA8& nd, const uint8_t* __restrict__ w8, const h16* __restrict__ wh, const float* __restrict__ wf,
                                                    const h16* pin, size_t sIdx, int copMax, int uBytes, unsigned char* smem,
-                                                   h16* __restrict__ value, h16* __restrict__ piA, h16* __restrict__ piB, h16* __restrict__ wdl, h16* __restrict__ ml) {
+                                                   h16* __restrict__ value, h16* __restrict__ piA, h16* __restrict__ piB, h16* __restrict__ wdl, h16* __restrict__ ml,
+                                                   int polOff = 0, PolicyEpi epi = PolicyEpi()) {
     constexpr int C = CTILES * 32, ldx = C + 8, ldq = C + 16, ctiles = CTILES, TPW = (2 * CTILES + 7) / 8;
     constexpr int KSX = C / 64;                                          // k-steps of a K = C GEMM (expand, value conv) and of one 3x3 tap
     constexpr int XD = CTILES > 4 ? 1 : 4;                               // expand stream: tiles in flight (48 / 64 registers)
@@ -216,6 +223,7 @@ __device__ __forceinline__ void narrow_position_a8(const NetDescA8& nd, const ui
     uint8_t* U = Xq + 65 * ldq;                                         // union region
     h16* Sin = reinterpret_cast<h16*>(U);                               // [65][ldi] input staging
     uint8_t* Sq = U;                                                    // [65][ldq] policy trunk output, codes
+    h16* Pol = reinterpret_cast<h16*>(U + polOff);                      // WT: [160][64] policy staging, PolicyEpi's scratch behind it
     h16* Y1 = reinterpret_cast<h16*>(U);                                // [chunk][66]
     uint8_t* Y2 = U + (size_t)copMax * 132;                             // [64][chunk64 + 16] codes
     float* Pf = reinterpret_cast<float*>(U + uBytes);                   // b1[copMax] b2[copMax] s1[copMax] b3[C]
@@ -427,9 +435,18 @@ __device__ __forceinline__ void narrow_position_a8(const NetDescA8& nd, const ui
             const float mx = fmaxf(lo[0], fmaxf(lo[1], lo[2]));
             const float e0 = __expf(lo[0] - mx), e1 = __expf(lo[1] - mx), e2 = __expf(lo[2] - mx);
             const float inv = 1.0f / (e0 + e1 + e2);
-            value[sIdx] = (h16)((e2 - e0) * inv);                       // win - loss
-            wdl[sIdx * 3 + 0] = (h16)lo[0]; wdl[sIdx * 3 + 1] = (h16)lo[1]; wdl[sIdx * 3 + 2] = (h16)lo[2];
-            ml[sIdx] = (h16)(1.0f / (1.0f + __expf(-lo[3])));
+            const h16 hv = (h16)((e2 - e0) * inv);                      // win - loss
+            const h16 hm = (h16)(1.0f / (1.0f + __expf(-lo[3])));
+            if constexpr (WT) {
+                auto bits = [](h16 x) { return __builtin_bit_cast(uint16_t, x); };
+                hmq::store2_wt(reinterpret_cast<uint16_t*>(value + sIdx), bits(hv));
+                for (int o = 0; o < 3; ++o) hmq::store2_wt(reinterpret_cast<uint16_t*>(wdl + sIdx * 3 + o), bits((h16)lo[o]));
+                hmq::store2_wt(reinterpret_cast<uint16_t*>(ml + sIdx), bits(hm));
+            } else {
+                value[sIdx] = hv;
+                wdl[sIdx * 3 + 0] = (h16)lo[0]; wdl[sIdx * 3 + 1] = (h16)lo[1]; wdl[sIdx * 3 + 2] = (h16)lo[2];
+                ml[sIdx] = hm;
+            }
         }
         __syncthreads();                                                 // Y1 (inside U) is about to be overwritten by Sq
     }
@@ -458,11 +475,24 @@ __device__ __forceinline__ void narrow_position_a8(const NetDescA8& nd, const ui
         for (int rg = 0; rg < 16; ++rg) {
             const int ch = ct * 32 + drow(rg, lane);
             const float v = e[rg] * wf[nd.pp_s + ch];
-            if (ch < 73) piA[sIdx * HM_POLICY_VALUES + ch * 64 + sqL] = (h16)v;
+            if constexpr (WT) Pol[ch * 64 + sqL] = (h16)v;                // [160][64] staging behind Sq
+            else if (ch < 73) piA[sIdx * HM_POLICY_VALUES + ch * 64 + sqL] = (h16)v;
             else if (ch < 146) piB[sIdx * HM_POLICY_VALUES + (ch - 73) * 64 + sqL] = (h16)v;
         }
     }
     __syncthreads();                                                     // Sq lies in U: the next position's input staging overwrites it
+    if constexpr (WT && PolicyEpi::present) {
+        epi(Pol, reinterpret_cast<unsigned char*>(Pol + 160 * 64));
+    } else if constexpr (WT) {
+        // 146 planes x 64 squares = 1168 chunks of 8 halfs: one write-through 16-byte store each
+        for (int i = tid; i < 146 * 8; i += 512) {
+            const int ch = i >> 3, part = i & 7;
+            const hmq::u32x4q v = *reinterpret_cast<const hmq::u32x4q*>(Pol + ch * 64 + part * 8);
+            h16* dst = (ch < 73 ? piA + sIdx * HM_POLICY_VALUES + ch * 64 : piB + sIdx * HM_POLICY_VALUES + (ch - 73) * 64) + part * 8;
+            hmq::store16_wt(dst, v);
+        }
+        __syncthreads();                                                 // Pol lies in U too
+    }
 }
 
 }  // namespace hmn

@@ -48,18 +48,34 @@ struct A8LdsPlan {
     int copMax, uBytes;
     size_t ldsBytes;
 };
-inline A8LdsPlan a8_lds_plan(int C, int cinPad, int maxCop) {
+// minUnion: another tenant the union region must hold; tailBytes: LDS the caller keeps behind the layout (counted against the limit,
+// not part of ldsBytes)
+inline A8LdsPlan a8_lds_plan(int C, int cinPad, int maxCop, size_t minUnion = 0, size_t tailBytes = 0) {
     const size_t ldx = C + 8, ldq = C + 16, ldi = cinPad + 8;
     auto bytes_for = [&](int cm) {
-        size_t u = std::max({(size_t)cm * 132 + (size_t)64 * (cm + 16), 65 * ldq, 65 * ldi * 2, (size_t)36 * C * 4});
+        size_t u = std::max({(size_t)cm * 132 + (size_t)64 * (cm + 16), 65 * ldq, 65 * ldi * 2, (size_t)36 * C * 4, minUnion});
         u = (u + 15) & ~(size_t)15;
         return std::make_pair(u, 64 * ldx * 2 + 65 * ldq + u + (3 * (size_t)cm + C) * 4 + ((((size_t)cm * 25 + 7) & ~(size_t)7) * 2) + ((size_t)C + 64) * 4);
     };
     int copMax = (std::max(64, maxCop) + 63) & ~63;
     if (const char* ce = std::getenv("HM_NET_COP_CHUNK")) copMax = std::min(copMax, std::max(64, std::atoi(ce) & ~63));   // (measurements, tests)
-    while (copMax > 64 && bytes_for(copMax).second > NARROW_LDS_LIMIT) copMax -= 64;
+    while (copMax > 64 && bytes_for(copMax).second + tailBytes > NARROW_LDS_LIMIT) copMax -= 64;
     const auto ub = bytes_for(copMax);
-    return {ub.second <= NARROW_LDS_LIMIT, copMax, (int)ub.first, ub.second};
+    return {ub.second + tailBytes <= NARROW_LDS_LIMIT, copMax, (int)ub.first, ub.second};
+}
+// The plan of the same layout for the serve form (narrow_position_a8<.., WT>: the evaluator role of the single-launch search): the
+// policy staging Pol[160][64] fp16 and the prior pipeline's scratch (stagingBytes together) lie behind Sq[65][C+16] inside the union
+// region, which is enlarged to hold them where the expansion's tenants leave it smaller (narrow trunks, or a small chunk); behind the
+// layout the evaluator role keeps its 16-byte item word.  The 384-channel trunk at its chunk of 320: 26 000 + 36 928 of 63 744 bytes.
+struct A8ServePlan {
+    bool ok;
+    int copMax, uBytes, polOff;                                          // polOff: bytes from the start of the union region to Pol
+    size_t ldsBytes;
+};
+inline A8ServePlan a8_serve_plan(int C, int cinPad, int maxCop, size_t stagingBytes) {
+    const size_t polOff = (65 * ((size_t)C + 16) + 15) & ~(size_t)15;
+    const A8LdsPlan pl = a8_lds_plan(C, cinPad, maxCop, polOff + stagingBytes, 16);
+    return {pl.ok, pl.copMax, pl.uBytes, (int)polOff, pl.ldsBytes};
 }
 
 // max(32, the widest `cop` of nd's blocks); requireMultipleOf32: a cop that is no positive multiple of 32 is refused (-1, *err set,

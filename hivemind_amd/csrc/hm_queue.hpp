@@ -223,10 +223,14 @@ struct ServeArgs {
 }  // namespace hmq
 
 struct hm_net;
-// hm_net.hip: 1 when `net` can be the evaluator of the single-launch search (the narrow trunks: C = 64, 128, 384)
+// hm_net.hip: 1 when `net` can be the evaluator of the single-launch search (the narrow fp16 trunks: C = 64, 128, 384; a network on
+// native FP8 MFMA once hm_net_set_serve has selected its serve form)
 extern "C" int hm_net_can_serve(const hm_net* net);
 // hm_net.hip: 1 when one position takes this network's evaluator much longer than a game needs to collect a batch (the 384-channel trunk)
 int hm_net_serve_is_slow(const hm_net* net);
-// hm_net.hip: what the evaluator role needs of a network handle
-struct hm_net_serve_info { const void* d_nd; const void* d_wh; const void* d_wf; int C, k5, copMax, uHalfs; size_t ldsBytes; };
+// hm_net.hip: what the evaluator role needs of a network handle.  form: which evaluator role runs it (the kernel table hm_sp_search
+// picks); HM_SERVE_A8 (narrow_position_a8): d_nd is a NetDescA8, d_w8 the e4m3 codes, uBytes / polOff the union region and the
+// policy staging's place in it (a8_serve_plan), and uHalfs is unused
+enum { HM_SERVE_F16 = 0, HM_SERVE_A8 = 1 };
+struct hm_net_serve_info { const void* d_nd; const void* d_wh; const void* d_wf; int C, k5, copMax, uHalfs; size_t ldsBytes; const void* d_w8; int uBytes, polOff, form; };
 int hm_net_serve_info_get(const hm_net* net, hm_net_serve_info* out);

@@ -17,8 +17,11 @@
 // Compiled once per search role: -DHM_ROLLOUT_MODE=0 (node pool in LDS), 1 (tree walked in place), 2 (several games per search
 // workgroup), each for the network variants of rollout_kernel(); diagnostic builds (-DHM_SINGLE_TU) include this file from
 // hm_search.hip instead, so that the probes of hm_prof.hpp land in the one translation unit that reads them.
+// k_rollout_a8 (the same launch with the evaluator on native FP8 MFMA: serve_role_a8) is defined here and instantiated by
+// hm_rollout_a8.hip, which includes this file with HM_ROLLOUT_A8 defined.
 #include "hm_search_device.hpp"
 #include "hm_net_device.hpp"
+#include "hm_net_a8_device.hpp"
 #include <cstdlib>
 
 namespace hms {
@@ -594,6 +597,49 @@ __device__ __forceinline__ void serve_role(unsigned char* smem, unsigned* s_item
         __hip_atomic_fetch_add(hmq::G32(&a.q->consOut), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
+// The evaluator role on native FP8 MFMA: the loop of serve_role, statement for statement (kept as a copy: serve_role's instantiations
+// must compile to what they were), around the serve form of narrow_position_a8 (hm_net_a8_device.hpp; eight waves).  rn.uBytes /
+// rn.polOff: the union region that holds the policy staging behind Sq, and where (a8_serve_plan).  No spin of its own: pop_item's.
+template <int CTILES, bool K5>
+__device__ __forceinline__ void serve_role_a8(unsigned char* smem, unsigned* s_item, const RolloutNet& rn, const hmq::ServeArgs& a) {
+    using namespace hmn;
+    const NetDescA8& nd = *static_cast<const NetDescA8*>(rn.nd);
+    const uint8_t* w8 = static_cast<const uint8_t*>(rn.w8);
+    const h16* wh = static_cast<const h16*>(rn.wh);
+    const float* wf = static_cast<const float*>(rn.wf);
+    unsigned long long ticks = 0, count = 0;
+    if (threadIdx.x == 0) __hip_atomic_fetch_add(hmq::G32(&a.q->consIn), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+        if (threadIdx.x == 0) {
+            const unsigned it = hmq::pop_item(a.q);
+            if (it != hmq::IT_POISON) hmq::acquire_agent();
+            *s_item = it;
+        }
+        __syncthreads();
+        const unsigned it = *s_item;
+        if (it == hmq::IT_POISON) break;                            // uniform
+        if (a.abortAfter && threadIdx.x == 0 && __hip_atomic_load(hmq::G32(&a.q->tail), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= a.abortAfter)
+            __hip_atomic_store(hmq::G32(&a.q->error), 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // test hook, as in serve_role
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        const int g = hmq::item_game(it), buf = hmq::item_buf(it), row = hmq::item_row(it);
+        const size_t r = (size_t)g * 8 + row;
+        PriorEpi epi{&a, (size_t)(g * 2 + buf) * 8 + row, g, (it & hmq::IT_ROOT) != 0};
+        narrow_position_a8<CTILES, K5, true, PriorEpi>(nd, w8, wh, wf, reinterpret_cast<const h16*>(a.planes[buf]) + r * HM_PLANE_VALUES, r, rn.copMax, rn.uBytes, smem,
+                                                       reinterpret_cast<h16*>(a.value[buf]), reinterpret_cast<h16*>(a.piA[buf]), reinterpret_cast<h16*>(a.piB[buf]),
+                                                       reinterpret_cast<h16*>(a.wdl[buf]), reinterpret_cast<h16*>(a.ml[buf]), rn.polOff, epi);
+        hmq::drain_stores();                                        // every wave's write-through stores of the heads and the priors have left
+        __syncthreads();                                            // (also: every thread has read s_item)
+        if (threadIdx.x == 0) {
+            __hip_atomic_fetch_add(hmq::G32(&a.done[g * 2 + buf]), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ticks += __builtin_amdgcn_s_memrealtime() - t0; ++count;
+        }
+    }
+    if (threadIdx.x == 0) {
+        if (a.clkSum && count) { atomicAdd(a.clkSum, ticks); atomicAdd(a.clkCnt, count); }
+        __hip_atomic_fetch_add(hmq::G32(&a.q->served), (unsigned)count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(hmq::G32(&a.q->consOut), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
 
 // ONE launch: workgroups [0, searchWgs) search, the others evaluate.  Both roles take a whole CU, so the grid is resident at once
 // when it has no more workgroups than the device has CUs.  WAVES = waves per workgroup:
@@ -619,8 +665,24 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_rollout(Pools pl, Params prm,
     }
 }
 
+// The same launch with the evaluator on native FP8 MFMA (serve_role_a8; a network hm_net_set_serve has put into its serve form):
+// always eight waves — the form has no four-wave body —, the search workgroups as in k_rollout<.., 8>.  A kernel of its own, not a
+// parameter of k_rollout, and instantiated by hm_rollout_a8.hip, so that the fp16 kernels, their names and their objects stay as they are.
+template <int MODE, int CTILES, bool K5>
+__global__ __launch_bounds__(512, 1) void k_rollout_a8(Pools pl, Params prm, SearchIo io, RolloutNet rn, hmq::ServeArgs a, int nGames, int perWg, int searchWgs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if ((int)blockIdx.x < searchWgs) {
+        if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= COLLECT_THREADS) __builtin_amdgcn_endpgm();
+        if constexpr (MODE == 2) search_role_mg(smem, pl, prm, io, nGames, perWg, (int)blockIdx.x, searchWgs);
+        else search_role<MODE == 0>(smem, pl, prm, io, (int)blockIdx.x);
+    } else {
+        serve_role_a8<CTILES, K5>(smem, reinterpret_cast<unsigned*>(smem + rn.itemOff), rn, a);
+    }
+}
+
 }  // namespace hms
 
+#ifndef HM_ROLLOUT_A8    // (hm_rollout_a8.hip includes this file for the roles above and brings its own table)
 // ---- host side: instantiation table of this translation unit's mode ---------------------------------------------------------
 #ifndef HM_ROLLOUT_MODE
 #error "compile with -DHM_ROLLOUT_MODE=0|1|2 (or include from hm_search.hip with HM_SINGLE_TU, which defines the three entry points itself)"
@@ -665,3 +727,4 @@ const void* hm_rollout_kernel_mode2(int ctiles, int k5, int narrow8, int* waves)
 const void* HM_ROLLOUT_ENTRY(HM_ROLLOUT_MODE)(int ctiles, int k5, int narrow8, int* waves) { return rollout_kernel<HM_ROLLOUT_MODE>(ctiles, k5, narrow8, waves); }
 #endif
 }
+#endif  // HM_ROLLOUT_A8

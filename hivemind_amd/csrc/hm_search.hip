@@ -1239,6 +1239,10 @@ int hm_sp_search_consumers(const hm_sp* sp) {
 const void* hm_rollout_kernel_mode0(int ctiles, int k5, int narrow8, int* waves);
 const void* hm_rollout_kernel_mode1(int ctiles, int k5, int narrow8, int* waves);
 const void* hm_rollout_kernel_mode2(int ctiles, int k5, int narrow8, int* waves);
+// hm_rollout_a8.hip, likewise: the k_rollout_a8 instantiation (evaluator on native FP8 MFMA; always eight waves), or nullptr
+const void* hm_rollout_a8_kernel_mode0(int ctiles, int k5);
+const void* hm_rollout_a8_kernel_mode1(int ctiles, int k5);
+const void* hm_rollout_a8_kernel_mode2(int ctiles, int k5);
 
 // The whole node-budget search of every slot hm_sp_begin_search left in the searching state, with the native evaluator, as ONE
 // kernel launch (hm_rollout.hip: k_rollout — game workgroups and evaluator workgroups joined by the device-side queue of
@@ -1260,7 +1264,11 @@ int hm_sp_search(hm_sp* sp, const hm_net* net, const hm_eval_io* io, double* sea
     const int actNow = std::min(sp->lastBeginActive > 0 ? sp->lastBeginActive : sp->nGames, sp->nGames);
     static const int min8 = [] { const char* e = std::getenv("HM_ROLLOUT_WAVES8_MIN_ACT"); return e ? std::atoi(e) : HM_ROLLOUT_WAVES8_MIN_ACT_DEFAULT; }();
     const int narrow8 = actNow >= min8 ? 1 : 0;
-    const void* kern = mode == 0 ? hm_rollout_kernel_mode0(ni.C / 32, ni.k5, narrow8, &waves) : mode == 1 ? hm_rollout_kernel_mode1(ni.C / 32, ni.k5, narrow8, &waves) : hm_rollout_kernel_mode2(ni.C / 32, ni.k5, narrow8, &waves);
+    const void* kern = nullptr;
+    if (ni.form == HM_SERVE_A8) {
+        waves = 8;
+        kern = mode == 0 ? hm_rollout_a8_kernel_mode0(ni.C / 32, ni.k5) : mode == 1 ? hm_rollout_a8_kernel_mode1(ni.C / 32, ni.k5) : hm_rollout_a8_kernel_mode2(ni.C / 32, ni.k5);
+    } else kern = mode == 0 ? hm_rollout_kernel_mode0(ni.C / 32, ni.k5, narrow8, &waves) : mode == 1 ? hm_rollout_kernel_mode1(ni.C / 32, ni.k5, narrow8, &waves) : hm_rollout_kernel_mode2(ni.C / 32, ni.k5, narrow8, &waves);
     if (!kern) return hm_fail(HM_ERR_INVALID, "no single-launch search kernel for this trunk width");
     // dynamic LDS: the larger of the two roles' layouts (they overlay each other); the evaluator's item word sits behind its own layout
     const size_t ldsSearch = search_lds_bytes(mode) + (mode == 0 ? (size_t)sp->prm.nodeCap * sizeof(Node) : 0);
@@ -1321,7 +1329,7 @@ int hm_sp_search(hm_sp* sp, const hm_net* net, const hm_eval_io* io, double* sea
     sio.planes[0] = static_cast<uint16_t*>(io->planes[0]); sio.planes[1] = static_cast<uint16_t*>(io->planes[1]);
     for (int b = 0; b < 2; ++b) sio.out[b] = NetOut{a.value[b], a.piA[b], a.piB[b], a.wdl[b], a.ml[b]};
     sio.q = q; sio.done = done; sio.diag = reinterpret_cast<hmq::GameDiag*>(sp->d_queue + lay.diag); sio.netSel = nullptr; sio.ldsNodes = sp->searchLdsNodes;
-    RolloutNet rn{ni.d_nd, ni.d_wh, ni.d_wf, ni.copMax, ni.uHalfs, itemOff};
+    RolloutNet rn{ni.d_nd, ni.d_wh, ni.d_wf, ni.copMax, ni.uHalfs, itemOff, ni.d_w8, ni.uBytes, ni.polOff};
     int nGames = sp->nGames, perWgArg = perWg, searchWgsArg = searchWgs;
     void* args[] = {&sp->pl, &sp->prm, &sio, &rn, &a, &nGames, &perWgArg, &searchWgsArg};
     (void)hipEventRecord(sp->evT0, sT);            // HIP events on the stream the kernel is launched on: its launch duration

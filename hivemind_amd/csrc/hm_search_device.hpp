@@ -1864,7 +1864,8 @@ struct SearchLdsMg {
 __host__ __device__ constexpr size_t search_lds_bytes(int mode) {
     return ((mode == 0 ? sizeof(SearchLds<true>) : mode == 1 ? sizeof(SearchLds<false>) : sizeof(SearchLdsMg)) + 15) & ~(size_t)15;
 }
-// what the evaluator role needs of the network (hm_net_serve_info), plus where its item word sits in LDS
-struct RolloutNet { const void* nd; const void* wh; const void* wf; int copMax, uHalfs; unsigned itemOff; };
+// what the evaluator role needs of the network (hm_net_serve_info), plus where its item word sits in LDS; w8 / uBytes / polOff: the
+// evaluator role on native FP8 MFMA (serve_role_a8) only
+struct RolloutNet { const void* nd; const void* wh; const void* wf; int copMax, uHalfs; unsigned itemOff; const void* w8; int uBytes, polOff; };
 
 }  // namespace hms

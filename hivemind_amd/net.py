@@ -469,11 +469,13 @@ class FusedNet:
     not overlap each other (one stream); split_error() tells whether a launch gave up.
     acts="fp8" (with weights="fp8"; trunks of 128 / 384 channels): the same five GEMM families on the native FP8 MFMA, their
     activations quantised to e4m3 too with one static power-of-two scale per tensor (hm_net_create_a8) — calibrated on
-    calibration=planes by calibrate_act_scales, or given as act_scales=[2 * nblocks + 2 powers of two].  Not the default."""
+    calibration=planes by calibrate_act_scales, or given as act_scales=[2 * nblocks + 2 powers of two].  Not the default.
+    serve=True (acts="fp8" only): the serve form (hm_net_set_serve) — the network can be the evaluator of the single-launch search
+    (SearchEngine.search_persistent, the self-play driver's one launch per ply); without it such a network is refused there."""
 
     MAXB, CIN_PAD = 16, 80
 
-    def __init__(self, model: RiseV3, device="cuda", weights="fp16", pair=False, split=0, max_rows=1024, acts="fp16", calibration=None, act_scales=None):
+    def __init__(self, model: RiseV3, device="cuda", weights="fp16", pair=False, split=0, max_rows=1024, acts="fp16", calibration=None, act_scales=None, serve=False):
         import ctypes as C
         import numpy as np
         from ._lib import lib, check
@@ -487,6 +489,9 @@ class FusedNet:
         if acts not in ("fp16", "fp8"):
             raise ValueError("acts must be 'fp16' or 'fp8'")
         a8 = acts == "fp8"
+        if serve and not a8:
+            raise ValueError("serve=True needs weights='fp8' and acts='fp8' (the fp16 forms that can serve the single-launch search do so as they are)")
+        self.serve = bool(serve)
         if a8:
             if weights != "fp8":
                 raise ValueError("acts='fp8' needs weights='fp8'")
@@ -791,6 +796,8 @@ class FusedNet:
         create = self._lib.hm_net_create_a8 if a8 else self._lib.hm_net_create_w8
         self._check(create(self.desc.ctypes.data, self.desc.size, self.w8.data_ptr(), self.wh.data_ptr(), self.wf.data_ptr(), C.byref(h)))
         self.handle = h
+        if self.serve:
+            self._check(self._lib.hm_net_set_serve(h, 1))
 
     def close(self):
         if getattr(self, "handle", None):

@@ -354,9 +354,18 @@ int hm_net_create_w8(const int32_t* desc, size_t desc_ints, const void* d_w8, co
  * One static power-of-two scale per quantised tensor (2 * nblocks + 2 of them, calibrated by net.py calibrate_act_scales);
  * desc = hmn::NetDescA8 as int32s (net.py FusedNet(weights="fp8", acts="fp8")), d_w8 = the codes as [K/64][tile][lane][32]
  * (32-byte aligned), d_wf additionally the folded scales and 1 / sa.  Trunks of 128 / 384 channels, input planes padded to 80.
- * The handle serves hm_net_forward, hm_net_forward_groups[_timed] and hm_net_destroy; hm_net_can_serve is 0 for it,
- * hm_net_set_pair, hm_net_set_split and hm_net_profile refuse it, and it has no plan file. */
+ * The handle serves hm_net_forward, hm_net_forward_groups[_timed] and hm_net_destroy; hm_net_can_serve is 0 for it until
+ * hm_net_set_serve, hm_net_set_pair, hm_net_set_split and hm_net_profile refuse it, and it has no plan file. */
 int hm_net_create_a8(const int32_t* desc, size_t desc_ints, const void* d_w8, const void* d_wh, const void* d_wf, hm_net** out);
+/* The serve form of such a handle: on != 0 lets it be the evaluator of the single-launch search (hm_sp_search, and through it the
+ * self-play driver's one launch per searched ply) — the role Engine::enqueueInferenceHalf / synchronizeInferenceHalf
+ * (nn/engine.h:43-81) play for the reference's search threads, with the reduced-precision engine of nn/engine.cc:290-401 behind
+ * them; on == 0 takes it back.  hm_net_can_serve is 1 afterwards.  The evaluator keeps a leaf's policy logits and the prior
+ * pipeline's scratch in LDS behind the policy trunk's tile (37 KB); HM_ERR_INVALID when that does not fit one CU's LDS beside the
+ * network's tiles, and for every handle that is not on native FP8 MFMA.  Opt-in: without the call such a handle keeps refusing
+ * hm_sp_search.  The stand-alone forward is unaffected, and a search gives the results of the lockstep calls with the same handle
+ * bit for bit. */
+int hm_net_set_serve(hm_net* net, int on);
 /* The pair form of the forward for this handle: on != 0 makes hm_net_forward, hm_net_forward_groups[_timed] and hm_net_profile
  * run two positions (rows 2p, 2p + 1) per 4-wave workgroup, every weight fragment multiplying M = 128 rows; on == 0 restores the
  * previous form.  Results are bit-identical to the other forms, rows outside a group's count stay untouched.  fp16 trunks of 64 or
@@ -394,7 +403,8 @@ int hm_net_create_xboard(const int32_t* desc, size_t desc_ints, const int32_t* t
 /* The tail kernel of such a handle alone on caller-supplied trunk features d_features = fp16 [n][64][C] (16-byte aligned). */
 int hm_net_xboard_tail(const hm_net* net, const void* d_features, const void* d_planes, int n,
                        void* d_value, void* d_pi_a, void* d_pi_b, void* d_wdl, void* d_moves_left, void* stream);
-/* 1 when `net` can be the evaluator of the single-launch search (hm_sp_search), else 0 (fp16 trunks of 64 / 128 / 384 channels only). */
+/* 1 when `net` can be the evaluator of the single-launch search (hm_sp_search), else 0 (fp16 trunks of 64 / 128 / 384 channels, and
+ * networks on native FP8 MFMA after hm_net_set_serve). */
 int hm_net_can_serve(const hm_net* net);
 int hm_net_destroy(hm_net* net);
 int hm_net_forward(const hm_net* net, const void* d_planes, int n,
